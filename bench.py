@@ -2,7 +2,18 @@
 """bench.py - BASELINE.json's metric on the MI355X-native hot path, one JSON line per run.
 
 usage  : python bench.py [--config balance|transport|transport_2pkg|navigation|football] [--gpus N] [--strong|--weak]
-                         [--steps K] [--warmup W]            (no flags: config 2 - balance, 32768 envs, n_agents=4 - on 1 GPU)
+                         [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
+                                                             (no flags: config 2 - balance, 32768 envs, n_agents=4 - on 1 GPU)
+plain  : without --full the run does what the headline needs and nothing else: set-up, W warm-up steps, ONE window of exactly
+         K timed steps (`--repeats R`: R windows), the line with `value` / `ms_per_step`.  Every other object described below
+         (`world_step`, `environment_step`, `persistent_rollout`, `other_configs`, `attached_reference`, `roofline`,
+         `cpu_baseline`, `cpu_port`, `parity`, `rollout_gather`, `sharded_rollout`) is measured with --full only (five windows
+         by default there), where the line is what it was before the option existed.
+outputs: `--dump-outputs DIR` writes what the LAST timed step returned to its caller - per agent the observation, the reward
+         and the info entries, and the done flags - as DIR/<name>.npy (float32; above 64 MB in all, a fixed seeded sample of
+         the environments, the rows in DIR/env_index.npy).  Same arguments, same inputs: the timed steps start W steps after
+         a seeded reset with pre-drawn seeded actions, so two builds can be compared output for output.  (Where World.step
+         alone is the headline - --fused, --no-attached - the array is `state`, [B, entities, 6].)
 metric : env-steps/sec (batch x substeps) on the configuration's scenario (SURVEY.md 8d's table: cfg 2 balance 32768 envs,
          cfg 3 transport 16384 (+ the n_packages=2 box-box variant), cfg 4 navigation n_agents=8 65536, cfg 5 football 5v5 131072)
 step   : ONE call of the REFERENCE's ``Environment.step`` (environment.py:325) - the object ``vmas.make_env(...,
@@ -95,8 +106,16 @@ def parse_args():
     ap.add_argument("--gate-us", type=float, default=100.0,
                     help="untimed spin kernel in front of every timed window (microseconds; 0 = none): the K launches are "
                          "queued behind it, so the HIP events hold K back-to-back steps and not the host's first-launch latency")
-    ap.add_argument("--repeats", type=int, default=5,
-                    help="the K-step window is timed this many times (each between its own fences); `value` = the median window")
+    ap.add_argument("--repeats", type=int, default=0,
+                    help="the K-step window is timed this many times (each between its own fences); `value` = the median window "
+                         "(0 = 1 in a plain run, so that --steps is the number of timed steps, and 5 with --full)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline as well: World.step alone, this package's own Environment.step, the "
+                         "persistent rollout, the other configurations, the attached-reference legs, HBM traffic by the PMC "
+                         "counters, the CPU baselines and the same-run parity (minutes); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float32; a fixed, seeded sample of the environments where all of it would exceed 64 MB)")
     ap.add_argument("--num-envs", type=int, default=0, help="environments PER GPU (0 = the configuration's)")
     ap.add_argument("--n-agents", type=int, default=0, help="balance / navigation: agents (0 = the configuration's)")
     ap.add_argument("--lanes", type=int, default=0, help="lanes per environment (0 = library default)")
@@ -648,7 +667,45 @@ def attached_reference_leg(name, kw, B, device, n=300, brief=False):
     return out
 
 
-def attached_headline(name, kw, B, device, steps, warmup, repeats, clock_warmup, dist, seed=0):
+DUMP_BUDGET = 60 << 20  # bytes of float32 that --dump-outputs writes at most
+
+
+def dump_arrays(dump_dir, arrays):
+    """--dump-outputs: every tensor of ``arrays`` (name -> [B, ...], environments first) as DIR/<name>.npy in float32.  All
+    of them together stay below DUMP_BUDGET: a larger output is cut to a sample of the environments - the same sorted
+    rows of every array, drawn once with a fixed seed (written beside them as env_index.npy, float64)."""
+    import numpy as np
+    import torch
+
+    os.makedirs(dump_dir, exist_ok=True)
+    B = next(iter(arrays.values())).shape[0]
+    assert all(t.shape[0] == B for t in arrays.values())
+    total = sum(t.numel() for t in arrays.values()) * 4
+    index = None
+    if total > DUMP_BUDGET:
+        keep = max(1, int(B * DUMP_BUDGET / (total + 8 * B)))
+        index = torch.randperm(B, generator=torch.Generator(device="cpu").manual_seed(20240229))[:keep].sort().values
+        np.save(os.path.join(dump_dir, "env_index.npy"), index.numpy().astype(np.float64))
+    for name, t in arrays.items():
+        t = t.detach().to("cpu", torch.float32)
+        np.save(os.path.join(dump_dir, name + ".npy"), np.ascontiguousarray((t if index is None else t[index]).numpy()))
+    return {"dir": dump_dir, "arrays": sorted(arrays), "envs": B, "envs_written": B if index is None else int(index.numel())}
+
+
+def dump_env_outputs(dump_dir, agent_names, obs, rews, dones, infos):
+    """What Environment.step returned - per agent the observation, the reward and every info entry, and the done flags."""
+    import torch
+
+    arrays = {"done": dones}
+    for i, a in enumerate(agent_names):
+        for kind, val in (("obs", obs[i]), ("reward", rews[i]), ("info", infos[i])):
+            for key, t in (val.items() if isinstance(val, dict) else [(None, val)]):
+                if torch.is_tensor(t):
+                    arrays[f"{kind}_{a}" + ("" if key is None else f"_{key}")] = t
+    return dump_arrays(dump_dir, {k.replace("/", "_").replace(" ", "_"): v for k, v in arrays.items()})
+
+
+def attached_headline(name, kw, B, device, steps, warmup, repeats, clock_warmup, dist, seed=0, dump_dir=None):
     """THE HEADLINE (north_star; round-5 review item 7): `steps` calls of the REFERENCE's ``Environment.step`` - the object
     ``vmas.make_env(..., device='cuda')`` returns, after ``attach()`` with its defaults: the one-launch kernel where a post-step
     kernel covers the configuration, the reference's action asserts kept, the reference's batch-global broad phase - between
@@ -671,8 +728,9 @@ def attached_headline(name, kw, B, device, steps, warmup, repeats, clock_warmup,
         torch.cuda.synchronize()
 
     def run(n, start=0):
-        for k in range(n):
+        for k in range(n - 1):
             env.step(cycle[(start + k) % 25])
+        return env.step(cycle[(start + n - 1) % 25]) if n > 0 else None  # (what the caller of the last step receives)
 
     out = {"fused": h.fused is not None, "fused_reason": h.fused_reason, "exact_broad_phase": bool(h.exact_broad_phase),
            "exact_form": h.backend.exact_form(), "substeps": int(getattr(env.world, "_substeps", 1)),
@@ -686,6 +744,9 @@ def attached_headline(name, kw, B, device, steps, warmup, repeats, clock_warmup,
         while time.perf_counter() - t_clock < clock_warmup:
             run(50)
             torch.cuda.synchronize()
+        # (the clock warm-up above is as many steps as fit its time: back to the seeded post-reset state, so that the timed
+        #  steps start from the same state, and end in the same outputs, in every run with the same arguments)
+        env.reset(seed=seed)
         run(warmup)
         windows = []
         for _ in range(max(1, repeats)):
@@ -693,11 +754,13 @@ def attached_headline(name, kw, B, device, steps, warmup, repeats, clock_warmup,
             e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             t0 = time.perf_counter()
             e0.record()
-            run(steps, start=warmup)
+            last = run(steps, start=warmup)
             e1.record()
             fence()
             wall = time.perf_counter() - t0
             windows.append((max_over_ranks(e0.elapsed_time(e1) * 1e-3, device), max_over_ranks(wall, device)))
+        if dump_dir and last is not None:
+            out["dumped"] = dump_env_outputs(dump_dir, [a.name for a in env.agents], *last)
     h.detach()
     out["windows"] = windows
     return out
@@ -974,7 +1037,7 @@ def measure(name, args, device, shard, dist, rank, world_size, brief=False):
 
     # ---- the same K launches on ONE queue (what rocprofv3's per-kernel durations describe); then the headline
     single = None
-    if not args.fused and not brief and be.queues(min(EPISODE, steps)) > 1:
+    if args.full and not args.fused and not brief and be.queues(min(EPISODE, steps)) > 1:
         be.set_queues(1)
         run(warmup)
         ev_1, wall_1, _ = timed(lambda n: run(n, start=warmup), steps)
@@ -1062,9 +1125,63 @@ def brief_line(r):
     return out
 
 
+def plain_line(args, cfg, scaling, shard, head, world_size, ranks_seen):
+    """The line of a plain run (no --full): the headline of `attached_headline` and what describes it; `value`, `ms_per_step`
+    and `repeats` computed as in the full line."""
+    B, steps, kw = shard.local_envs, args.steps, config_kwargs(args.config, args.n_agents)
+    hw_ = sorted(head["windows"], key=lambda x: x[1])
+    ev_h, wall_h = hw_[len(hw_) // 2]
+    return {
+        "metric": f"env-steps/sec (batch x substeps) on '{cfg['scenario']}'",
+        "value": world_size * B * head["substeps"] * steps / wall_h,
+        "unit": "env-steps/s",
+        "n_gpus": world_size,
+        "ranks_seen": ranks_seen,
+        "steps": steps,
+        "warmup": args.warmup, "clock_warmup_s": args.clock_warmup,
+        "ms_per_step": wall_h / steps * 1e3,
+        "repeats": {"windows": len(hw_), "steps_per_window": steps,
+                    "ms_per_step_min": min(x[1] for x in hw_) / steps * 1e3, "ms_per_step_median": wall_h / steps * 1e3,
+                    "ms_per_step_max": max(x[1] for x in hw_) / steps * 1e3,
+                    "gpu_ms_per_step_median": ev_h / steps * 1e3,
+                    "note": "each window = exactly `steps` env.step calls between barrier + synchronize fences; `value` and "
+                            "`ms_per_step` are the median window by the wall clock, gpu_ms_per_step the same window by HIP events"},
+        "higher_is_better": True,
+        "scaling": scaling,
+        "vs_baseline": None,
+        "dtype": "f32",
+        "data": "synthetic",
+        "full": False,
+        "library_build_id": _library_build_id(),
+        "value_is": "env-steps/s through the REFERENCE's own vmas.make_env(..., device='cuda') / Environment.step() after "
+                    "attach() with its defaults - the reference's action asserts kept, the reference's batch-global "
+                    "broad phase - K calls between barrier + synchronize fences, the host included (wall clock, MAX over "
+                    "ranks; median window).  Everything else the benchmark measures (World.step alone, this package's own "
+                    "Environment.step, the other configurations, roofline, CPU baselines, parity): --full",
+        "config": {
+            "workload": f"BASELINE config {cfg['cfg']}: the reference's {cfg['scenario']} {kw}, {B} envs/GPU "
+                        f"({shard.num_envs} in all), vmas.make_env(device='cuda') + attach(), Environment.step() with "
+                        f"fresh random actions every step",
+            "baseline_config": cfg["cfg"], "scenario": cfg["scenario"], "scenario_kwargs": kw,
+            "num_envs_per_gpu": B,
+            "global_envs": shard.num_envs,
+            "substeps": head["substeps"],
+            "launch": f"{head.get('launches_per_env_step', '?')} launch(es) per env.step (+ the asserts' two small "
+                      f"launches): ingest prologue + World.step + reward/observation/done/info epilogue",
+            "kernel": f"{head['kernel']} step kernel, exact_form {head['exact_form']} (1 = lazy, inside the launch)",
+            "parallelism": f"env-sharded x{world_size}",
+        },
+        "headline": {k: v for k, v in head.items() if k != "windows"},
+    }
+
+
 # ------------------------------------------------------------------------------------------------ main
 def main():
     args = parse_args()
+    if not args.repeats:
+        args.repeats = 5 if args.full else 1
+    if not args.full and not args.dry_run:  # a plain run times the headline and nothing beside it
+        args.no_cpu_baseline = args.no_fused = args.no_gather = args.no_other_configs = args.no_traffic = True
     maybe_spawn(args)
     import torch
 
@@ -1140,15 +1257,14 @@ def main():
         traffic_child(args, device)
         return
 
-    r = measure(args.config, args, device, shard, dist, rank, world_size)
-    B, steps, kernel_s, n_queues = r["envs_per_gpu"], r["steps"], r["kernel_s"], r["n_queues"]
-    # the headline: the same metric through the reference's own vmas.make_env() / Environment.step() (every rank its shard)
-    head = None
-    if not args.no_attached and not args.fused:
+    dump_dir = args.dump_outputs if rank == 0 else None
+
+    def headline():
+        """The headline: the metric through the reference's own vmas.make_env() / Environment.step() (every rank its shard)."""
         ok = 1
         try:
-            head = attached_headline(args.config, r["kwargs"], B, device, steps, r["warmup"], args.repeats, args.clock_warmup, dist,
-                                     seed=shard.seed(0))
+            head = attached_headline(args.config, config_kwargs(args.config, args.n_agents), shard.local_envs, device, args.steps,
+                                     args.warmup, args.repeats, args.clock_warmup, dist, seed=shard.seed(0), dump_dir=dump_dir)
         except Exception as e:  # noqa: BLE001 (the reference is not importable here: the native Environment.step is the headline)
             head, ok = {"error": repr(e)[:500]}, 0
         if dist is not None:  # (all ranks or none: a rank without the reference must not leave the others in a barrier - it
@@ -1156,6 +1272,27 @@ def main():
             dist.all_reduce(t_ok, op=dist.ReduceOp.MIN)
             if int(t_ok.item()) == 0 and "error" not in head:
                 head = {"error": "another rank could not attach the reference"}
+        return head
+
+    # a plain run: the headline alone.  (World.step alone is timed only where it is the headline: --fused, --no-attached, or
+    # the reference cannot be attached here - the line then says so, `headline_fallback`)
+    head = None
+    if not args.full and not args.no_attached and not args.fused:
+        head = headline()
+        if "windows" in head:
+            if rank == 0:
+                print(json.dumps(plain_line(args, cfg, scaling, shard, head, world_size, ranks_seen)), flush=True)
+            if dist is not None:
+                dist.barrier()
+                dist.destroy_process_group()
+            return
+
+    r = measure(args.config, args, device, shard, dist, rank, world_size)
+    B, steps, kernel_s, n_queues = r["envs_per_gpu"], r["steps"], r["kernel_s"], r["n_queues"]
+    if args.full and not args.no_attached and not args.fused:
+        head = headline()
+    if dump_dir and not (head is not None and "dumped" in head):  # World.step is the headline: the state its last step left
+        r["dumped"] = dump_arrays(dump_dir, {"state": r["w"]._packed_state()[:, :, :B].permute(2, 0, 1)})
     windows = r["windows"]
     kw = r["kwargs"]
 
@@ -1290,6 +1427,8 @@ def main():
                                         "could not be made - " + head["error"])
         if args.share_gpu:
             out["share_gpu"] = "TESTING: every rank on cuda:0 over gloo - the N > 1 code path, not a measurement"
+        if "dumped" in r:
+            out["dumped"] = r["dumped"]
         if world_size == 1 and not args.no_traffic and not args.fused:
             try:
                 traffic, detail = measure_traffic(args, n_queues)
@@ -1316,7 +1455,7 @@ def main():
             out["rollout_gather"] = gather
         if others is not None:
             out["other_configs"] = others
-        if world_size == 1 and not args.no_attached and not args.fused:
+        if args.full and world_size == 1 and not args.no_attached and not args.fused:
             try:
                 out["attached_reference"] = attached_reference_leg(args.config, kw, B, device)
             except Exception as e:  # noqa: BLE001 (the reference is not importable here, or does not run on this device)

@@ -4,7 +4,7 @@
 # Stages:
 #   tests-new        the attach(fused) tests + the tests touched this round (fast feedback)
 #   tests            the whole -m gpu suite + smoke()
-#   bench            bench.py default (every leg) + the driver-style invocation
+#   bench            bench.py --full (every leg) + the driver-style invocation (a plain run: the headline alone)
 #   bench-configs    the full line of every other configuration
 #   attached         only the attached_reference legs of all five configurations
 #   ab LIB [LIB..] -- CMD...   A/B of libraries: CMD (a scripts/bench_*.py line printer) under each VMAS_HIP_LIB, twice, interleaved
@@ -44,7 +44,7 @@ while [ $# -gt 0 ]; do
     python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -1
     ;;
   bench)
-    ( time python bench.py > $OUT/${TAG}_bench_line_default.json 2> $OUT/bench_default.err ) 2>&1 | grep real
+    ( time python bench.py --full > $OUT/${TAG}_bench_line_default.json 2> $OUT/bench_default.err ) 2>&1 | grep real
     tail -3 $OUT/bench_default.err
     python $S/show_line.py $OUT/${TAG}_bench_line_default.json
     python bench.py --gpus 1 --steps 20 --warmup 5 --no-cpu-baseline > $OUT/${TAG}_bench_line_driver_style.json 2> $OUT/bench_driver_style.err
@@ -52,7 +52,7 @@ while [ $# -gt 0 ]; do
     ;;
   bench-configs)
     for C_ in transport transport_2pkg navigation football; do
-      python bench.py --config $C_ > $OUT/${TAG}_bench_line_$C_.json 2> $OUT/bench_$C_.err; python $S/show_line.py $OUT/${TAG}_bench_line_$C_.json brief; tail -2 $OUT/bench_$C_.err
+      python bench.py --full --config $C_ > $OUT/${TAG}_bench_line_$C_.json 2> $OUT/bench_$C_.err; python $S/show_line.py $OUT/${TAG}_bench_line_$C_.json brief; tail -2 $OUT/bench_$C_.err
     done
     ;;
   attached)
@@ -85,7 +85,7 @@ while [ $# -gt 0 ]; do
   evidence)
     # the bench command itself under rocprofv3.  (1) the HEADLINE of round 6: env.step of the attached reference environment - its
     # one-launch kernel rated at the physics' bytes + the actions / observations / rewards / done / info (657 B per environment)
-    BENCH="python $R/bench.py --no-cpu-baseline --no-fused --no-other-configs --no-traffic --steps 2000 --warmup 200 --repeats 3"
+    BENCH="python $R/bench.py --full --no-cpu-baseline --no-fused --no-other-configs --no-traffic --steps 2000 --warmup 200 --repeats 3"
     RATED=step_kernel_spec_multi:env bash $S/gpu_counters.sh ${TAG}_bench_q1 657 1700 32768 -- $BENCH > /dev/null 2>&1
     grep -h "sustained\|traffic / alg\|share of wave\|median" $OUT/${TAG}_bench_q1_pmc_summary.txt | head
     # (2) the physics-only launches (`world_step`), as in rounds 1-5

@@ -14,14 +14,16 @@ def r(x, n=2):
 
 
 es = d.get("environment_step", {})
-print("line:", {"value": r(d["value"], 0), "ms_per_step": r(d["ms_per_step"], 5), "frac": r(d["roofline"]["frac"], 4),
-                "traffic_x": r(d["roofline"].get("traffic_over_algorithmic"), 3),
+rf = d.get("roofline", {})  # (a plain line - no --full - carries the headline alone)
+print("line:", {"value": r(d["value"], 0), "ms_per_step": r(d["ms_per_step"], 5), "frac": r(rf.get("frac"), 4),
+                "traffic_x": r(rf.get("traffic_over_algorithmic"), 3),
                 "env_step_us": r(es.get("us_per_step")), "env_gpu_us": r(es.get("gpu_us_per_step")),
                 "bound_us": r(es.get("bound", {}).get("gpu_us_per_step")), "rollout_us": r(es.get("rollout", {}).get("us_per_step"))})
 ws = d.get("world_step")
 if ws:
     print("world_step:", {"value": r(ws["value"], 0), "ms_per_step": r(ws["ms_per_step"], 5), "frac": r(ws["roofline"]["frac"], 4),
                           "traffic_x": r(ws["roofline"].get("traffic_over_algorithmic"), 3)})
+if ws or not d.get("full", True):
     print("headline:", d.get("headline"), {k: r(v, 5) for k, v in d["repeats"].items() if k != "note"})
 if brief:
     sys.exit(0)

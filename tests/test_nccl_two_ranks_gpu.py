@@ -4,7 +4,7 @@ devices are visible (the single-GPU test boxes): the first multi-GPU box exercis
 * a sharded `balance` environment per rank on its own GPU (real libvmas_hip.so), a 4-step rollout collected straight into
   the packed gather layout, ONE all_gather_into_tensor: every rank finds its own block where its shard range says and
   the peer's block equal to what the peer computed (exchanged checksums);
-* `python bench.py --gpus 2` end to end: the line says n_gpus 2, both ranks' step times, the gather rates.
+* `python bench.py --full --gpus 2` end to end: the line says n_gpus 2, both ranks' step times, the gather rates.
 """
 import json
 import os
@@ -114,7 +114,7 @@ def test_two_rank_nccl_sharded_rollout_gather(num_envs):
 def test_bench_two_gpus_end_to_end():
     _need_two()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "50", "--warmup", "10",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "50", "--warmup", "10",
                           "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -128,10 +128,10 @@ def test_bench_two_gpus_end_to_end():
 
 
 def test_bench_two_gpus_strong_scaling_config():
-    """`--config navigation --gpus 2`: BASELINE config 4 sharded (strong scaling: 65 536 environments in all)."""
+    """`--full --config navigation --gpus 2`: BASELINE config 4 sharded (strong scaling: 65 536 environments in all)."""
     _need_two()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--config", "navigation", "--steps", "50",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--config", "navigation", "--steps", "50",
                           "--warmup", "10", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
@@ -140,12 +140,12 @@ def test_bench_two_gpus_strong_scaling_config():
 
 
 def test_bench_n_greater_1_code_path_on_one_gpu():
-    """`bench.py --gpus 2 --share-gpu` (testing mode: both ranks on cuda:0, process group over gloo): the N > 1 code path of the
+    """`bench.py --full --gpus 2 --share-gpu` (testing mode: both ranks on cuda:0, process group over gloo): the N > 1 code path of the
     line - environment sharding, barrier + synchronize fences, max over ranks, the attached headline on EVERY rank, the
     per-rank roofline - runs on the one-GPU boxes too.  Its numbers mean nothing (two processes share a device); its shape
     is what the driver's N = 2 / 4 / 8 runs will print."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT")}
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--share-gpu", "--no-gather", "--steps", "30",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--share-gpu", "--no-gather", "--steps", "30",
                           "--warmup", "5", "--no-cpu-baseline"], env=env, capture_output=True, text=True, timeout=1200)
     assert out.returncode == 0, out.stderr[-3000:]
     d = json.loads([l for l in out.stdout.splitlines() if l.startswith("{")][-1])
