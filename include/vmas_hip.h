@@ -194,6 +194,27 @@ int vmas_world_step_n(VmasWorld* w, float* state, float* agent_ft, int64_t ld, i
 int vmas_world_rollout(VmasWorld* w, float* state, float* agent_ft, int64_t ld, int64_t ft_step_stride,
                        int32_t n_steps, const VmasStepArgs* args /* may be NULL */, void* stream);
 
+/* The vector-Jacobian product of World.step (differentiable simulation: csrc/vmas_vjp.hip, DESIGN.md "Backward of
+ * World.step").  Served: worlds whose statically collidable pairs are all VMAS_PAIR_SS, without joints and without
+ * VMAS_F_LIN_FRICTION / VMAS_F_ANG_FRICTION, stepped without a per-environment entity_gravity tensor, and whose
+ * 64-environment tile (checkpoints of every substep included) fits the 160 KiB of LDS.  Everything else is refused:
+ * lines, boxes, joints, friction, tensor gravity, the LIDAR, a second derivative.
+ * vmas_world_step_vjp_check: 0 if vmas_world_step_vjp can serve this world; -1 + vmas_last_error() naming the first
+ * offending entity or pair (or the byte counts) if not.  No GPU work. */
+int vmas_world_step_vjp_check(VmasWorld* w);
+/* VJP of ONE vmas_world_step(w, state, agent_ft, ld, NULL).  state_in [E][6][ld] / ft_in [A][3][ld]: the buffers as they
+ * were BEFORE that step; g_state_out [E][6][ld], g_ft_out [A][3][ld] (may be NULL = zero): cotangents of what the step
+ * wrote (the state, and the agent forces as the step left them - clamped where the agent has max_f / f_range / max_t /
+ * t_range); g_state_in, g_ft_in: the cotangents of state_in and ft_in, written for columns < batch only (the caller
+ * zero-fills the padding) and distinct from every input buffer.  The launch re-runs the step's substeps from state_in
+ * with the forward's own device functions, so every clamp and contact decision is the forward's; at a kink (a clamp
+ * exactly at its bound) the convention is torch.clamp's / torch.where's.  Non-finite inputs give unspecified cotangents.
+ * fp32, no float atomics: two runs on the same inputs are bitwise equal.  Asynchronous on `stream`, allocates nothing,
+ * never waits. */
+int vmas_world_step_vjp(VmasWorld* w, const float* state_in, const float* ft_in, int64_t ld,
+                        const float* g_state_out, const float* g_ft_out,
+                        float* g_state_in, float* g_ft_in, void* stream);
+
 /* A world-specialised kernel made at RUN TIME for this world: `code_object_path` is a gfx950 code object compiled from
  * csrc/vmas_spec_kernel.h with the tables of the schedule this world runs (the Python side generates and compiles it:
  * vectorizedmultiagentsimulator_amd/specialize.py, cached on disk).  The library loads it, reads the tables back out of

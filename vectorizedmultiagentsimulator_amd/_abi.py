@@ -288,6 +288,8 @@ EXPORTED_SYMBOLS = (
     "vmas_world_step",
     "vmas_world_step_n",
     "vmas_world_rollout",
+    "vmas_world_step_vjp_check",
+    "vmas_world_step_vjp",
     "vmas_world_pair_mask",
     "vmas_world_set_lidars",
     "vmas_world_cast_rays",
@@ -365,6 +367,10 @@ def load_library() -> C.CDLL:
     lib.vmas_world_step_n.restype = C.c_int
     lib.vmas_world_rollout.argtypes = [vp, vp, vp, i64, i64, i32, C.POINTER(StepArgs), vp]
     lib.vmas_world_rollout.restype = C.c_int
+    lib.vmas_world_step_vjp_check.argtypes = [vp]
+    lib.vmas_world_step_vjp_check.restype = C.c_int
+    lib.vmas_world_step_vjp.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp]
+    lib.vmas_world_step_vjp.restype = C.c_int
     lib.vmas_world_pair_mask.argtypes = [vp, vp, i64, vp, vp]
     lib.vmas_world_pair_mask.restype = C.c_int
     lib.vmas_world_set_lidars.argtypes = [vp, C.POINTER(LidarDesc), i32]

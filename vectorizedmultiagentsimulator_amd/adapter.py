@@ -387,7 +387,9 @@ def attach(env_or_world, backend_factory: Callable = _default_backend,
     action by then; False drops the check."""
     world = getattr(env_or_world, "world", env_or_world)
     if getattr(env_or_world, "grad_enabled", False):
-        raise NotImplementedError("grad_enabled=True needs the reference's autograd path; the HIP step has no backward")
+        raise NotImplementedError("grad_enabled=True needs the reference's autograd path: the adapter rebinds world.step to the "
+                                  "in-place HIP step, which is not on the autograd tape.  The backward kernel serves this "
+                                  "package's own worlds only (make_env(..., grad_enabled=True)); widening the adapter is out of scope")
     profile, reason = None, "fused=False"
     if fused is not False:
         from .attached_env import FusedEnvStep, plan_fuse

@@ -232,9 +232,14 @@ class HipWorld:
         n_substeps: int = 0,
         stream=None,
         exact: bool = False,
+        state: Optional[torch.Tensor] = None,
+        agent_ft: Optional[torch.Tensor] = None,
     ) -> None:
         """World.step() for the whole batch, asynchronous on the (current) stream.  ``exact``: the reference's
-        batch-global broad phase re-evaluated at every substep (include/vmas_hip.h, VmasStepArgs.exact_broad_phase)."""
+        batch-global broad phase re-evaluated at every substep (include/vmas_hip.h, VmasStepArgs.exact_broad_phase).
+        ``state`` / ``agent_ft``: packed buffers to step in place of the adopted ones (differentiable.py steps clones)."""
+        state = self.state if state is None else self._packed_like(state, self.state, "state")
+        agent_ft = self.agent_ft if agent_ft is None else self._packed_like(agent_ft, self.agent_ft, "agent_ft")
         args = A.StepArgs()
         args.exact_broad_phase = 1 if exact else 0
         args.pair_mask = self._dptr(pair_mask)
@@ -246,10 +251,57 @@ class HipWorld:
         args.entity_gravity = self._dptr(entity_gravity)
         args.first_substep, args.n_substeps = first_substep, n_substeps
         rc = self.lib.vmas_world_step(
-            self._h, self._dptr(self.state), self._dptr(self.agent_ft), self.ld, C.byref(args), self._stream(stream)
+            self._h, self._dptr(state), self._dptr(agent_ft), self.ld, C.byref(args), self._stream(stream)
         )
         if rc != 0:
             raise VmasHipError(A.last_error())
+
+    @staticmethod
+    def _packed_like(t: torch.Tensor, like: torch.Tensor, name: str) -> torch.Tensor:
+        if t.shape != like.shape or t.dtype != like.dtype or t.device != like.device or not t.is_contiguous():
+            raise VmasHipError(f"{name}: expected a contiguous {like.dtype} tensor of shape {tuple(like.shape)} on {like.device}, "
+                               f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+        return t
+
+    # ------------------------------------------------------------------ backward of World.step
+    def vjp_supported(self) -> Optional[str]:
+        """None if ``step_vjp`` serves this world, else why not (include/vmas_hip.h, vmas_world_step_vjp_check: sphere-sphere
+        pairs only, no joints, no friction; and no per-environment gravity tensor, which is an input of the step the
+        backward kernel does not take)."""
+        why = getattr(self, "_vjp_why", False)
+        if why is False:
+            why = None
+            for i, e in enumerate(self.spec.entities):
+                if e.per_env_gravity:
+                    why = f"vmas_world_step_vjp: entity {i} has a per-environment gravity tensor, which the backward kernel does not serve"
+                    break
+            if why is None and self.lib.vmas_world_step_vjp_check(self._h) != 0:
+                why = A.last_error()
+            self._vjp_why = why
+        return why
+
+    def step_vjp(self, state_in: torch.Tensor, ft_in: torch.Tensor, g_state: torch.Tensor,
+                 g_ft: Optional[torch.Tensor] = None, stream=None):
+        """Vector-Jacobian product of ONE ``step()`` (no optional inputs) in one launch of the backward kernel
+        (csrc/vmas_vjp.hip).  ``state_in`` [E, 6, ld] / ``ft_in`` [A, 3, ld]: the packed buffers as they were before the
+        step; ``g_state`` / ``g_ft`` (None = zero): cotangents of the buffers as the step left them.  Returns
+        ``(g_state_in, g_ft_in)``, zero in the padding columns.  Asynchronous on the (current) stream."""
+        why = self.vjp_supported()
+        if why is not None:
+            raise VmasHipError(why)
+        state_in = self._packed_like(state_in, self.state, "state_in")
+        ft_in = self._packed_like(ft_in, self.agent_ft, "ft_in")
+        g_state = self._packed_like(g_state.contiguous(), self.state, "g_state")
+        if g_ft is not None:
+            g_ft = self._packed_like(g_ft.contiguous(), self.agent_ft, "g_ft")
+        g_state_in, g_ft_in = torch.zeros_like(self.state), torch.zeros_like(self.agent_ft)
+        rc = self.lib.vmas_world_step_vjp(
+            self._h, self._dptr(state_in), self._dptr(ft_in), self.ld, self._dptr(g_state), self._dptr(g_ft),
+            self._dptr(g_state_in), self._dptr(g_ft_in), self._stream(stream)
+        )
+        if rc != 0:
+            raise VmasHipError(A.last_error())
+        return g_state_in, g_ft_in
 
     def make_stepper(self, exact: bool = False):
         """A zero-argument callable that enqueues ``World.step()`` without per-call inputs on the current stream: every
@@ -345,11 +397,11 @@ class HipWorld:
             raise VmasHipError(A.last_error())
         return self._mask
 
-    def step_exact(self, joint_fixed_rot=None, entity_gravity=None, stream=None) -> None:
+    def step_exact(self, joint_fixed_rot=None, entity_gravity=None, stream=None, state=None, agent_ft=None) -> None:
         """World.step() with the reference's batch-global broad phase (core.py:2797-2801) re-evaluated at every
         substep: ONE launch for batches of at most 64 x CUs environments (mask + grid barrier inside the step kernel),
         a mask launch + a substep launch per substep beyond (the library decides)."""
-        self.step(None, joint_fixed_rot, entity_gravity, 0, 0, stream, exact=True)
+        self.step(None, joint_fixed_rot, entity_gravity, 0, 0, stream, exact=True, state=state, agent_ft=agent_ft)
 
     def step_exact_launches(self, joint_fixed_rot=None, entity_gravity=None, stream=None) -> None:
         """The same step as explicit launches (``vmas_world_pair_mask`` + a one-substep ``vmas_world_step`` with that

@@ -633,6 +633,7 @@ class World:
         gravity: Tuple[float, float] = (0.0, 0.0),
         exact_broad_phase: Optional[bool] = None,
         lanes_per_env: int = 0,
+        grad_enabled: bool = False,
     ):
         assert batch_dim > 0, f"Batch dim must be greater than 0, got {batch_dim}"
         self._batch_dim = batch_dim
@@ -661,6 +662,10 @@ class World:
         #: overlapping whenever another one sits in its band.
         self.exact_broad_phase = (batch_dim < EXACT_AUTO_BELOW) if exact_broad_phase is None else bool(exact_broad_phase)
         self._lanes_per_env = lanes_per_env
+        #: True = ``step()`` stays on the autograd tape (differentiable.py: the backward is ONE launch of the backward kernel):
+        #: it returns NEW packed tensors instead of stepping in place, the geometric queries take their torch forms, and a
+        #: full ``reset`` starts from fresh tensors.  Sphere-only worlds (``HipWorld.vjp_supported``); first order only.
+        self.grad_enabled = bool(grad_enabled)
         # geometric queries answered by ONE kernel launch per state version (GPU worlds)
         self._query_list: List[Tuple[str, int, int]] = []
         self._query_index: Dict[Tuple[str, int, int], int] = {}
@@ -725,8 +730,9 @@ class World:
         self._query_cache = None
 
     def _query(self, kind: str, a: Entity, b: Entity) -> Optional[Tensor]:
-        """Row of the fused query kernel for (kind, a, b), or None on non-GPU worlds."""
-        if self._device.type != "cuda":
+        """Row of the fused query kernel for (kind, a, b), or None on non-GPU worlds (and under ``grad_enabled``: the torch
+        forms of geometry.py stay on the tape)."""
+        if self._device.type != "cuda" or self.grad_enabled:
             return None
         key = (kind, a._index, b._index)
         be = self._get_backend()
@@ -824,6 +830,9 @@ class World:
     def reset(self, env_index: Optional[int]):
         self._query_cache = None
         self._packed_state()
+        if self.grad_enabled and env_index is None:
+            # a new episode starts a new tape: fresh zero tensors instead of in-place writes into the last step's outputs
+            self._state, self._agent_ft = torch.zeros_like(self._state), torch.zeros_like(self._agent_ft)
         for e in self.entities:
             e._reset(env_index)
 
@@ -859,11 +868,16 @@ class World:
         """core.py:1972-2015 as ONE fused kernel launch (or 2 per substep in exact mode)."""
         be = self._get_backend()
         self._query_cache = None
-        jfr, eg = self._per_env_inputs()
-        if self.exact_broad_phase:
-            be.step_exact(joint_fixed_rot=jfr, entity_gravity=eg)
+        if self.grad_enabled:
+            from .differentiable import world_step  # raises NotImplementedError with the reason for worlds it cannot serve
+
+            self._state, self._agent_ft = world_step(be, self._state, self._agent_ft, exact=self.exact_broad_phase)
         else:
-            be.step(joint_fixed_rot=jfr, entity_gravity=eg)
+            jfr, eg = self._per_env_inputs()
+            if self.exact_broad_phase:
+                be.step_exact(joint_fixed_rot=jfr, entity_gravity=eg)
+            else:
+                be.step(joint_fixed_rot=jfr, entity_gravity=eg)
         if self._dim_c > 0:  # _update_comm_state core.py:2910-2913
             for agent in self._agents:
                 if not agent.silent:
@@ -873,6 +887,7 @@ class World:
         """``step()`` with the environment's action ingest and the scenario's post-step fused into the
         same launch (fused.py / ``vmas_world_step_env``)."""
         assert self._dim_c == 0
+        assert not self.grad_enabled, "grad_enabled worlds step through World.step (the one-launch step has no backward)"
         be = self._get_backend()
         self._query_cache = None
         jfr, eg = self._per_env_inputs()
@@ -915,4 +930,6 @@ class World:
 
     def cast_rays_all(self) -> Tensor:
         """All Lidar sensors of all agents at once: [n_lidars, max_rays, ld]."""
+        if self.grad_enabled:
+            raise NotImplementedError("the LIDAR kernel has no backward: grad_enabled worlds cannot cast rays")
         return self._get_backend().cast_rays()

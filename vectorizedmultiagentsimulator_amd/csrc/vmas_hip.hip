@@ -54,6 +54,7 @@
 #include "../../include/vmas_hip.h"
 #include "../../include/vmas_debug_hip.h"
 #include "vmas_step_types.h"
+#include "vmas_vjp.h"
 
 #include "vmas_step_device.h"
 
@@ -1046,6 +1047,7 @@ struct VmasWorld {
   int queues = 0;
   bool host_only = false;  // a PLANNING world (device_id -1): schedules are built on the host, nothing is uploaded or launched
   bool use_spec = true;    // launch the world-specialised kernel when the schedule matches one (vmas_world_set_specialized)
+  vmas::vjp::Plan vjp;     // the backward kernel of World.step (vmas_vjp.hip): its table and tile layout, or why it refuses this world
   static constexpr int MAX_QUEUES = 4;
   hipStream_t side[MAX_QUEUES - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_QUEUES - 1] = {nullptr, nullptr, nullptr};
@@ -2341,6 +2343,11 @@ int vmas_world_create(const VmasWorldDesc* d, int32_t batch, int32_t device_id, 
     }
   }
   w->dev_ents = ents;
+  {
+    const vmas::vjp::WorldConst vc = {W.substeps, W.sub_dt, W.gx, W.gy, W.has_gravity, W.xs, W.ys, W.k, W.c_coll};
+    vmas::vjp::make_plan(vc, d->entities, d->n_entities, d->n_agents, d->pairs, d->n_pairs, d->n_joints, &w->vjp);
+    if (!host_only && w->vjp.ok && vmas::vjp::upload(&w->vjp)) return -1;
+  }
   if (!host_only) HIP_TRY(upload(&w->d_mpairs, mp));
   if (!host_only) {  // exact broad phase: barrier word + four mask slots (in-kernel form), one mask (launch-per-substep form)
     const size_t mw = (size_t)(d->n_pairs + 31) / 32;
@@ -2400,6 +2407,7 @@ void vmas_world_destroy(VmasWorld* w) {
   if (w->adapt.copied) (void)hipEventDestroy(w->adapt.copied);
   (void)hipFree(w->cp.d_blob); (void)hipFree(w->cp.d_trig);
   (void)hipFree(w->d_mpairs); (void)hipFree(w->d_trace);
+  vmas::vjp::release(&w->vjp);
   (void)hipFree(w->d_lidars); (void)hipFree(w->d_targets); (void)hipFree(w->d_angles); (void)hipFree(w->d_queries);
   (void)hipFree(w->d_angles_cs);
   delete w;
@@ -2557,6 +2565,26 @@ int vmas_world_get_queues(const VmasWorld* w, int32_t n_steps) { return w ? queu
 
 int vmas_world_step(VmasWorld* w, float* state, float* agent_ft, int64_t ld, const VmasStepArgs* args, void* stream) {
   return step_impl(w, state, agent_ft, ld, args, stream, 1, 0);
+}
+
+int vmas_world_step_vjp_check(VmasWorld* w) {
+  if (!w) return fail("vmas_world_step_vjp_check: null world");
+  if (!w->vjp.ok) return fail("vmas_world_step_vjp: %s", w->vjp.why);
+  return 0;
+}
+
+int vmas_world_step_vjp(VmasWorld* w, const float* state_in, const float* ft_in, int64_t ld, const float* g_state_out,
+                        const float* g_ft_out, float* g_state_in, float* g_ft_in, void* stream) {
+  if (!w) return fail("vmas_world_step_vjp: null world");
+  if (!state_in || !ft_in || !g_state_out || !g_state_in || !g_ft_in)
+    return fail("vmas_world_step_vjp: null buffer (only g_ft_out may be null)");
+  if (ld < w->batch) return fail("vmas_world_step_vjp: ld (%lld) < batch (%d)", (long long)ld, w->batch);
+  if (!w->vjp.ok) return fail("vmas_world_step_vjp: %s", w->vjp.why);
+  if (w->host_only) return fail("vmas_world_step_vjp: a planning world (device -1) has no device to launch on");
+  int cur = -1;
+  if (hipGetDevice(&cur) != hipSuccess || cur != w->device) HIP_TRY(hipSetDevice(w->device));
+  return vmas::vjp::launch(w->vjp, w->device, w->batch, state_in, ft_in, (long)ld, g_state_out, g_ft_out, g_state_in, g_ft_in,
+                           (hipStream_t)stream);
 }
 
 int vmas_world_rollout(VmasWorld* w, float* state, float* agent_ft, int64_t ld, int64_t ft_step_stride, int32_t n_steps,

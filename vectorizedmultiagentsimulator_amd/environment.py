@@ -40,10 +40,18 @@ class Environment:
         graph: bool = False,
         fused: Optional[bool] = None,
         specialize: Optional[bool] = None,
+        grad_enabled: bool = False,
         **kwargs,
     ):
         self.scenario = scenario
         self.use_graph = graph
+        #: the reference's keyword (environment.py:77): actions are not detached and ``world.step`` stays on the autograd
+        #: tape (core.World.grad_enabled).  The fused paths and the captured graph have no backward: off, and refused if asked for
+        self.grad_enabled = bool(grad_enabled)
+        if self.grad_enabled:
+            assert not fused, "grad_enabled=True cannot be combined with fused=True (the fused step has no backward)"
+            assert not graph, "grad_enabled=True cannot be combined with graph=True (a captured step is not on the autograd tape)"
+            fused = False
         self.fused = fused
         self._graph = None
         self.num_envs = num_envs
@@ -53,6 +61,7 @@ class Environment:
         self.clamp_action = clamp_actions
         self.validate_actions = validate_actions
         self.world: World = scenario.env_make_world(num_envs, self.device, **kwargs)
+        self.world.grad_enabled = self.grad_enabled
         self.agents: List[Agent] = self.world.policy_agents
         self.n_agents = len(self.agents)
         if self.world.dim_c > 0 and any(not a.silent for a in self.agents):
@@ -211,7 +220,9 @@ class Environment:
         return torch.randint(0, n, (self.num_envs, 1), device=self.device)
 
     def _set_action(self, action: Tensor, agent: Agent):
-        action = action.detach().to(self.device)
+        if not self.grad_enabled:  # environment.py:618
+            action = action.detach()
+        action = action.to(self.device)
         if self.validate_actions:
             assert not action.isnan().any()
         assert action.shape[1] == self.get_agent_action_size(agent), (
@@ -493,6 +504,7 @@ def make_env(
     graph: bool = False,
     fused: Optional[bool] = None,
     specialize: Optional[bool] = None,
+    grad_enabled: bool = False,
     **kwargs,
 ) -> Environment:
     """vmas.make_env(...) for the scenarios shipped in ``vectorizedmultiagentsimulator_amd.scenarios``."""
@@ -506,5 +518,5 @@ def make_env(
     return Environment(
         scenario, num_envs=num_envs, device=device, continuous_actions=continuous_actions, max_steps=max_steps,
         seed=seed, clamp_actions=clamp_actions, validate_actions=validate_actions, graph=graph, fused=fused,
-        specialize=specialize, **kwargs,
+        specialize=specialize, grad_enabled=grad_enabled, **kwargs,
     )
