@@ -195,10 +195,16 @@ int vmas_world_rollout(VmasWorld* w, float* state, float* agent_ft, int64_t ld, 
                        int32_t n_steps, const VmasStepArgs* args /* may be NULL */, void* stream);
 
 /* The vector-Jacobian product of World.step (differentiable simulation: csrc/vmas_vjp.hip, DESIGN.md "Backward of
- * World.step").  Served: worlds whose statically collidable pairs are all VMAS_PAIR_SS, without joints and without
+ * World.step").  Served: worlds whose statically collidable pairs are each VMAS_PAIR_SS, VMAS_PAIR_LS or VMAS_PAIR_BS
+ * (the line or box movable or not, rotatable or not, the box hollow or solid), without joints and without
  * VMAS_F_LIN_FRICTION / VMAS_F_ANG_FRICTION, stepped without a per-environment entity_gravity tensor, and whose
  * 64-environment tile (checkpoints of every substep included) fits the 160 KiB of LDS.  Everything else is refused:
- * lines, boxes, joints, friction, tensor gravity, the LIDAR, a second derivative.
+ * VMAS_PAIR_LL / VMAS_PAIR_BL / VMAS_PAIR_BB, joints, friction, tensor gravity, the LIDAR, a second derivative.
+ * What is differentiated is the per-environment step, vmas_world_step with args == NULL (every static pair evaluated in
+ * every environment).  For sphere-sphere pairs that is also the reference's batch-global broad phase (their force is
+ * exactly 0 where the bounding circles do not overlap); a line-sphere or box-sphere force is non-zero in the LINE_MIN_DIST
+ * band past a line's tip or a box's corner, where the batch-global rule depends on the other environments: callers step
+ * such worlds with exact_broad_phase == 0 when they want this backward.
  * vmas_world_step_vjp_check: 0 if vmas_world_step_vjp can serve this world; -1 + vmas_last_error() naming the first
  * offending entity or pair (or the byte counts) if not.  No GPU work. */
 int vmas_world_step_vjp_check(VmasWorld* w);

@@ -1,0 +1,178 @@
+"""The backward kernel of World.step for line-sphere and box-sphere contacts, by the method of test_step_vjp_gpu.py.  Figures,
+the margin of the box edges and why (d)/1 sits at the bound (kernel 3.34e-6, 4 x 8.5e-7): DESIGN.md 3.4b."""
+import dataclasses
+
+import numpy as np
+import pytest
+import torch
+
+import test_step_vjp_gpu as spheres
+from test_step_vjp_gpu import CLAMPS, F64, bound_and_check, grads, make_inputs
+from vectorizedmultiagentsimulator_amd import _abi as A
+from vectorizedmultiagentsimulator_amd.core import Agent, Box, Landmark, Line, Sphere, World
+
+pytestmark = pytest.mark.gpu
+LMD, HALF_PI = np.float32(4.0 / 6e2), float(np.float32(torch.pi / 2))  # LINE_MIN_DIST, the forward's pi / 2
+f32 = lambda x: float(np.float32(x))  # noqa: E731
+norm = lambda t: torch.linalg.vector_norm(t, dim=0)  # noqa: E731
+unit = lambda th: torch.stack([torch.cos(th), torch.sin(th)])  # noqa: E731
+only_spheres = dict(collision_filter=lambda e: isinstance(e.shape, Sphere))  # (no line-line, box-line, box-box pair)
+#: world -> (sphere contacts, contacts (a, b, where on a, env % 2 or all), seed per batch: the first with every float64 margin >= 1e-4)
+WORLDS = {
+    "d": ([], [(0, 1, "interior", 0), (0, 1, "tip", 1)], {1: 0, 64: 0, 65: 0}),
+    "e": ([], [(0, 4, "interior", 0), (1, 5, "edge", 0), (2, 4, "edge", 1), (1, 5, "corner", 1)], {63: 0, 130: 2}),
+    "f": ([(4, 5)], [(0, 6, "interior", None), (1, 7, "tip", None), (2, 8, "edge", None), (3, 9, "corner", None)], {63: 0, 130: 74}),
+}
+
+
+def build_world(name, batch, device="cpu", **kw):
+    """Worlds (d), (e), (f) of DESIGN.md 3.4b.  LDS of (f): 10 x (8 + 4 x 5) + 2 x (28 + 4 + 2 + 5) + 2 x (28 + 4 + 4 + 5) = 440 rows
+    of 256 B leave 200 of 640; 45 sphere pairs x 2 + 40 line / box pairs x 5 = 290 rows: two runs."""
+    w = World(batch, device, **{"d": {}, "e": dict(substeps=2, x_semidim=1.0, y_semidim=1.0, gravity=(0.1, -0.2)), "f": dict(substeps=5)}[name], **kw)
+    n, fixed = {"d": (0, [("wall", Line(0.3))]), "e": (1, [("hollow", Box(0.24, 0.12, hollow=True)), ("mark", None)]), "f": (2, [])}[name]
+    for i in range(2 * n):  # the lines, then the solid boxes (mass 5: DESIGN.md 3.4b)
+        w.add_landmark(Landmark(f"shape_{i}", movable=True, rotatable=True, mass=5.0, shape=Line(0.3) if i < n else Box(0.3, 0.1), **only_spheres))
+    for label, shape in fixed:  # immovable; the mark collides with nothing
+        w.add_landmark(Landmark(label, shape=shape, collide=shape is not None, **only_spheres))
+    for i in range({"d": 1, "e": 2, "f": 10}[name]):
+        w.add_agent(Agent(f"agent_{i}", shape=Sphere(0.1), **(CLAMPS if name == "e" else {})))
+    return w
+
+
+def inputs(name, batch):
+    """make_inputs of the sphere tests, then sphere b r + LINE_MIN_DIST - delta (log-uniform over [2e-4, 3e-3]) off a's outline."""
+    spec, (ss, contacts, seeds) = build_world(name, batch).spec, WORLDS[name]
+    state, ft = make_inputs(spec, ss, batch, seeds[batch], name == "e")
+    U = lambda g=torch.Generator().manual_seed(seeds[batch] + 1000): torch.rand(batch, generator=g, dtype=F64)  # noqa: E731
+    for a, b, where, res in contacts:
+        D = spec.entities[a]
+        side, end = torch.sign(U() - 0.5), torch.sign(U() - 0.5)
+        if where in ("interior", "edge"):
+            point, phi = torch.stack([(1.2 * U() - 0.6) * D.length / 2, side * D.width / 2]), side * HALF_PI
+        else:  # 0.3 .. 1.2 rad off the axis, on the corner's side (end < 0: pi - phi)
+            point, phi = torch.stack([end * D.length / 2, side * D.width / 2]), (1 - end) * torch.pi / 2 + end * side * (0.3 + 0.9 * U())
+        local = point + (f32(np.float32(spec.entities[b].radius) + LMD) - 2e-4 * 15.0 ** U()) * unit(phi)
+        (c, s), on = unit(state[a, 4]), torch.arange(batch) % 2 == res if res is not None else torch.ones(batch, dtype=torch.bool)
+        state[b, 0:2] = torch.where(on, state[a, 0:2] + torch.stack([c * local[0] - s * local[1], s * local[0] + c * local[1]]), state[b, 0:2])
+    return spec, state, ft
+
+
+def shape_forces(spec, state, note):
+    """Force [E, 2, B] and torque [E, B] of the line-sphere and box-sphere pairs, every pair in every environment."""
+    k, c, ents = f32(spec.contact_margin), f32(spec.collision_force), spec.entities
+    F, T = [0 * state[e, 0:2] for e in range(len(ents))], [0 * state[e, 4] for e in range(len(ents))]
+
+    def segment(centre, u, half, p):  # -> the closest point, and how far the projection is from the clamp's kink
+        dot = ((centre - p) * u).sum(0)
+        return centre - dot.clamp(-half, half) * u, dot.abs() - half
+    for P in (P for P in spec.pairs if P.type != A.PAIR_SS):
+        Da, pa, pb, dm = ents[P.a], state[P.a, 0:2], state[P.b, 0:2], f32(np.float32(ents[P.b].radius) + LMD)
+        ax, half = [unit(state[P.a, 4]), unit(state[P.a, 4] + HALF_PI)], (f32(Da.length / 2), f32(Da.width / 2))
+        if P.type == A.PAIR_LS:
+            cp, kink = segment(pa, ax[0], half[0], pb)
+        else:  # the closest of the four edges' closest points, the first of equals
+            edges = [segment(pa + sg * half[i] * ax[i], ax[1 - i], half[1 - i], pb) for i in (0, 1) for sg in (1.0, -1.0)]
+            dist = torch.stack([norm(pb - q) for q, _ in edges])
+            pick = lambda ts: torch.stack(ts).gather(0, dist.argmin(0).expand(ts[0].shape)[None])[0]  # noqa: E731
+            cp, kink = pick([e[0] for e in edges]), pick([e[1] for e in edges])
+            # best against the other edges, as a displacement of the sphere; the same point is the same function
+            far, low = torch.stack([norm(q - cp) for q, _ in edges]), dist.min(0).values
+            note(((dist - low) * 2 * low / far.clamp_min(1e-9)).masked_fill(far < 1e-9, torch.inf).min(0).values, half[1])
+        note(kink, half[P.type == A.PAIR_BS])
+        v, solid = cp - pb, P.type == A.PAIR_BS and not Da.flags & A.F_HOLLOW  # a solid box pushes from the inner point, xm deep
+        xm = (v * (pa - cp)).sum(0) / norm(v) if solid else 0 * norm(v)
+        q, dm = cp + v / norm(v) * xm, dm + xm.abs()
+        d = pb - q
+        note(norm(d) - dm, dm)
+        f = c * d / norm(d) * (k * torch.logaddexp(torch.zeros_like(d[0]), (dm - norm(d)) / k))
+        f = torch.where((norm(d) < 1e-6) | (norm(d) > dm), torch.zeros_like(f), f)  # on the sphere; the opposite on a, at cp
+        F[P.b], F[P.a], T[P.a] = F[P.b] + f, F[P.a] - f, T[P.a] - ((cp - pa)[0] * f[1] - (cp - pa)[1] * f[0])
+    return torch.stack(F), torch.stack(T)
+
+
+def restate(spec, state, ft, margins=None):
+    """World.step (per-environment broad phase) substep by substep through the sphere tests' restatement: the line and box
+    pairs' F and T enter its vel (1 - drag) + F_spheres / m dt as a kick of F dt / (m (1 - drag)) to vel (drag: substep 0 only)."""
+    note = (lambda q, s: margins.append((q / s).detach().abs().min().item())) if margins is not None else (lambda q, s: None)
+    for s in range(spec.substeps):
+        ents = [dataclasses.replace(D, one_minus_drag=D.one_minus_drag if s == 0 else 1.0) for D in spec.entities]
+        F, T = shape_forces(spec, state, note)
+        lin, ang = (torch.tensor([f32(spec.sub_dt) / (f32(i) * f32(D.one_minus_drag)) if D.flags & fl else 0.0 for D, i in zip(ents, by)]).to(state)
+                    for fl, by in ((A.F_MOVABLE, [D.mass for D in ents]), (A.F_ROTATABLE, [D.inertia for D in ents])))
+        kick = torch.cat([0 * F, F * lin[:, None, None], 0 * T[:, None], (T * ang[:, None])[:, None]], dim=1)
+        state, ft_out = spheres.restate(dataclasses.replace(spec, substeps=1, entities=ents, pairs=[P for P in spec.pairs if P.type == A.PAIR_SS]), state + kick, ft, margins)
+    return state, ft_out
+
+
+def references(fn, leaves, w):  # gradients of fn(margins, *leaves) in float64 and float32; no float64 margin under 1e-4
+    margins = []
+    g64, out64 = grads(lambda *x: fn(margins, *x), leaves, w, F64)
+    assert min(margins) >= 1e-4, f"a branch quantity is within 1e-4 of its kink: {min(margins):.2e}"
+    return g64, grads(lambda *x: fn(None, *x), leaves, w, torch.float32)[0], out64
+
+
+@pytest.mark.parametrize("name,batch", [(n, b) for n, v in WORLDS.items() for b in v[2]])
+def test_step_vjp_of_line_and_box_contacts_against_float64_autograd(name, batch, monkeypatch):
+    spec, state, ft = inputs(name, batch)
+    w = [torch.randn(t.shape, generator=g, dtype=F64) for g in [torch.Generator().manual_seed(1)] for t in (state, ft)]
+    ref = (spec, state, ft, w, *references(lambda m, s, f: restate(spec, s, f, m), [state, ft], w))
+    monkeypatch.setattr(spheres, "reference", lambda *_: ref)  # the sphere test's body: forward to 1e-5, two runs bitwise equal, padding, the bound
+    spheres.test_step_vjp_against_float64_autograd(name, batch, True)
+
+
+def test_three_chained_world_steps_through_contacts_and_the_forward_under_grad():
+    (spec, state, ft), B, g = inputs("e", 63), 63, torch.Generator().manual_seed(2)
+    w = [torch.randn(6, 2, B, generator=g, dtype=F64), torch.randn(6, B, generator=g, dtype=F64)]
+    leaves = [ft[:, 0:2], state[1, 2:4], state[1, 5:6]]  # every step's forces, the box's initial velocity and angular velocity
+
+    def chain(m, F, v, a):
+        s = state.to(F.dtype)
+        s = torch.cat([s[:1], torch.cat([s[1, 0:2], v, s[1, 4:5], a])[None], s[2:]])
+        for _ in range(3):
+            s, _ = restate(spec, s, torch.cat([F, ft[:, 2:3].to(F.dtype)], dim=1), m)
+        return s[:, 0:2], s[:, 4]
+
+    g64, g32, _ = references(chain, leaves, w)
+    F, v1, a1 = (t.to(torch.float32).cuda().requires_grad_() for t in leaves)
+    ends = []
+    for grad in (False, True):  # without the tape first: the forward under grad_enabled is bitwise the per-environment step
+        with torch.set_grad_enabled(grad):
+            world = build_world("e", B, "cuda", grad_enabled=grad, **({} if grad else {"exact_broad_phase": False}))
+            world.reset(None)
+            for e, ent in enumerate(world.entities):
+                ent.set_pos(state[e, 0:2].T, None), ent.set_rot(state[e, 4:5].T, None)
+                ent.state.vel, ent.state.ang_vel = (v1.T, a1.T) if e == 1 else (state[e, 2:4].T, state[e, 5:6].T)
+            for _ in range(3):
+                for a, agent in enumerate(world.agents):
+                    agent.state.force, agent.state.torque = F[a].T, ft[a, 2:3].T
+                world.step()
+        ends.append((world._state.detach().clone(), world._agent_ft.detach().clone()))
+    assert all(torch.equal(x, y) for x, y in zip(*ends))
+    pos, rot = torch.stack([e.state.pos.T for e in world.entities]), torch.stack([e.state.rot[:, 0] for e in world.entities])
+    bound_and_check(torch.autograd.grad((pos * w[0].cuda()).sum() + (rot * w[1].cuda()).sum(), [F, v1, a1]), g64, g32, "chained e/63")
+
+
+def test_make_env_transport_gradient_of_the_rewards():
+    from vectorizedmultiagentsimulator_amd.environment import make_env
+    env = make_env("transport", num_envs=65, n_agents=2, grad_enabled=True, seed=5)
+    package, goal, g, B = env.scenario.packages[0], env.scenario.goal, torch.Generator().manual_seed(6), 65
+    for i, agent in enumerate(env.agents):  # agent 0 on the package's +x edge, agent 1 under it
+        reach = package.shape.length / 2 + f32(np.float32(agent.shape.radius) + LMD) - 2e-4 * 15.0 ** torch.rand(B, generator=g)
+        along = 0.04 * torch.rand(B, generator=g) - 0.02
+        agent.set_pos(package.state.pos.detach() + torch.stack([reach, along] if i == 0 else [along, -reach], dim=1).cuda(), None)
+    spec, rows = env.world.spec, [a._agent_index for a in env.agents]
+    state0, ft0 = env.world._state[:, :, :B].detach().cpu().to(F64), env.world._agent_ft[:, :, :B].detach().cpu().to(F64)
+    acts = [torch.rand(2, B, 2, generator=g, dtype=F64) * 1.6 - 0.8 for _ in range(2)]
+    mult = torch.stack([a.action.u_multiplier_tensor_on("cpu").to(F64) for a in env.agents])[:, None, :]
+
+    def rewards(m, a1):  # both agents get shaping before - shaping after of each step: the sum is 2 x (first - last shaping)
+        state, ft = state0.to(a1.dtype), ft0.to(a1.dtype)
+        for a in (a1, acts[1].to(a1.dtype)):
+            ft = ft.index_copy(0, torch.tensor(rows), torch.cat([(a * mult.to(a1.dtype)).transpose(1, 2), ft[rows, 2:3]], dim=1))
+            state, ft = restate(spec, state, ft, m)
+        return (-2 * env.scenario.shaping_factor * norm(state[package._index, 0:2] - state[goal._index, 0:2]),)
+
+    g64, g32, _ = references(rewards, [acts[0]], [torch.ones(B, dtype=F64)])
+    a1 = acts[0].to(torch.float32).cuda().requires_grad_()
+    rews = env.step(list(a1))[1] + env.step(list(acts[1].to(torch.float32).cuda()))[1]
+    bound_and_check(torch.autograd.grad(sum(r.sum() for r in rews), [a1]), g64, g32, "transport/65")

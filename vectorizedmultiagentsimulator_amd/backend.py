@@ -265,9 +265,9 @@ class HipWorld:
 
     # ------------------------------------------------------------------ backward of World.step
     def vjp_supported(self) -> Optional[str]:
-        """None if ``step_vjp`` serves this world, else why not (include/vmas_hip.h, vmas_world_step_vjp_check: sphere-sphere
-        pairs only, no joints, no friction; and no per-environment gravity tensor, which is an input of the step the
-        backward kernel does not take)."""
+        """None if ``step_vjp`` serves this world, else why not (include/vmas_hip.h, vmas_world_step_vjp_check: sphere-sphere,
+        line-sphere and box-sphere pairs only, no joints, no friction; and no per-environment gravity tensor, which is an
+        input of the step the backward kernel does not take)."""
         why = getattr(self, "_vjp_why", False)
         if why is False:
             why = None
@@ -282,7 +282,7 @@ class HipWorld:
 
     def step_vjp(self, state_in: torch.Tensor, ft_in: torch.Tensor, g_state: torch.Tensor,
                  g_ft: Optional[torch.Tensor] = None, stream=None):
-        """Vector-Jacobian product of ONE ``step()`` (no optional inputs) in one launch of the backward kernel
+        """Vector-Jacobian product of ONE ``step()`` (no optional inputs, ``exact=False``) in one launch of the backward kernel
         (csrc/vmas_vjp.hip).  ``state_in`` [E, 6, ld] / ``ft_in`` [A, 3, ld]: the packed buffers as they were before the
         step; ``g_state`` / ``g_ft`` (None = zero): cotangents of the buffers as the step left them.  Returns
         ``(g_state_in, g_ft_in)``, zero in the padding columns.  Asynchronous on the (current) stream."""

@@ -661,10 +661,13 @@ class World:
         #: environment - the same result only while SOME environment of the batch has the pair's bounding circles
         #: overlapping whenever another one sits in its band.
         self.exact_broad_phase = (batch_dim < EXACT_AUTO_BELOW) if exact_broad_phase is None else bool(exact_broad_phase)
+        self._exact_unspecified = exact_broad_phase is None
         self._lanes_per_env = lanes_per_env
         #: True = ``step()`` stays on the autograd tape (differentiable.py: the backward is ONE launch of the backward kernel):
         #: it returns NEW packed tensors instead of stepping in place, the geometric queries take their torch forms, and a
-        #: full ``reset`` starts from fresh tensors.  Sphere-only worlds (``HipWorld.vjp_supported``); first order only.
+        #: full ``reset`` starts from fresh tensors.  Worlds of sphere-sphere, line-sphere and box-sphere pairs
+        #: (``HipWorld.vjp_supported``); first order only.  With a line-sphere or box-sphere pair the step differentiated is the
+        #: per-environment one: an unspecified ``exact_broad_phase`` resolves to False, an explicit True is refused at ``step``.
         self.grad_enabled = bool(grad_enabled)
         # geometric queries answered by ONE kernel launch per state version (GPU worlds)
         self._query_list: List[Tuple[str, int, int]] = []
@@ -866,12 +869,23 @@ class World:
 
     def step(self):
         """core.py:1972-2015 as ONE fused kernel launch (or 2 per substep in exact mode)."""
+        exact = self.exact_broad_phase
+        if self.grad_enabled:
+            from .differentiable import EXACT_REFUSAL, has_shape_pairs, planning_refusal
+
+            spec = self.spec
+            if getattr(self, "_shape_pairs_of", None) is not spec:  # (asked once per spec)
+                self._shape_pairs_of, self._shape_pairs = spec, has_shape_pairs(spec)
+            if self._shape_pairs:  # the backward is the per-environment step's (DESIGN.md 3.4b)
+                if exact and not self._exact_unspecified:  # (a world refused for a pair, joint or friction says that first)
+                    raise NotImplementedError(planning_refusal(spec) or EXACT_REFUSAL)
+                exact = False
         be = self._get_backend()
         self._query_cache = None
         if self.grad_enabled:
             from .differentiable import world_step  # raises NotImplementedError with the reason for worlds it cannot serve
 
-            self._state, self._agent_ft = world_step(be, self._state, self._agent_ft, exact=self.exact_broad_phase)
+            self._state, self._agent_ft = world_step(be, self._state, self._agent_ft, exact=exact)
         else:
             jfr, eg = self._per_env_inputs()
             if self.exact_broad_phase:

@@ -26,10 +26,11 @@ struct Plan {
   WorldConst C{};
   int nE = 0, nA = 0, nP = 0;
   int nw = 1;                     // waves per 64-environment tile
-  int chunk = 0, n_chunks = 0;    // pairs evaluated between two block barriers (their rows fit the tile), and how many such runs
+  bool shapes = false;            // a kept pair is line-sphere or box-sphere: the kernel with their code is launched
+  int chunk = 0, n_chunks = 0;    // pairs of the largest run between two block barriers (sizes nw), and how many runs there are
   int row_pairs = 0, n_rows = 0;  // first pair row / rows of the tile (64 floats each)
   size_t lds_bytes = 0;
-  int o_ent = 0, o_pair = 0, o_ref = 0, o_cur = 0;  // word offsets into the table
+  int o_ent = 0, o_pair = 0, o_ref = 0, o_cur = 0, o_chk = 0;  // word offsets into the table
   std::vector<uint32_t> table;
   uint32_t* d_table = nullptr;
 };

@@ -1,13 +1,43 @@
 """``World.step`` on the autograd tape: the forward is the HIP step kernel, the backward ONE launch of the backward
 kernel (csrc/vmas_vjp.hip through ``HipWorld.step_vjp``) - no chain of small tensor ops, no tape of them.
 
-Served: sphere-only worlds (``HipWorld.vjp_supported()``; DESIGN.md "Backward of World.step").  First order only: the
-backward is ``once_differentiable``.
+Served: worlds whose pairs are sphere-sphere, line-sphere or box-sphere (``HipWorld.vjp_supported()``; DESIGN.md
+"Backward of World.step").  First order only: the backward is ``once_differentiable``.
+
+With a line-sphere or box-sphere pair the step that is differentiated is the per-environment one (``exact=False``): past
+a line's tip or a box's corner such a pair's force is non-zero where the bounding circles do not overlap, and there the
+reference's batch-global rule depends on the other environments of the batch, which a backward without communication
+between tiles cannot reproduce.  ``exact=True`` is refused for these worlds.
 """
 from __future__ import annotations
 
 import torch
 from torch.autograd.function import once_differentiable
+
+from . import _abi as A
+
+EXACT_REFUSAL = ("the backward kernel differentiates the per-environment step: a world with a line-sphere or box-sphere pair "
+                 "cannot be stepped with the batch-global broad phase (exact_broad_phase=True) under grad_enabled")
+
+
+def has_shape_pairs(spec) -> bool:
+    """True if a statically collidable pair of ``spec`` is line-sphere or box-sphere."""
+    return any(p.type in (A.PAIR_LS, A.PAIR_BS) for p in spec.pairs)
+
+
+def planning_refusal(spec):
+    """Why the backward kernel refuses ``spec`` (None: it does not), asked of a planning world: no GPU work."""
+    import ctypes as C
+
+    for i, e in enumerate(spec.entities):
+        if e.per_env_gravity:
+            return f"vmas_world_step_vjp: entity {i} has a per-environment gravity tensor, which the backward kernel does not serve"
+    lib, desc, h = A.load_library(), spec.to_ctypes(), C.c_void_p()
+    if lib.vmas_world_create(C.byref(desc.world), 1, -1, C.byref(h)) != 0:
+        return A.last_error()
+    why = None if lib.vmas_world_step_vjp_check(h) == 0 else A.last_error()
+    lib.vmas_world_destroy(h)
+    return why
 
 
 class _WorldStep(torch.autograd.Function):
@@ -33,9 +63,11 @@ def world_step(hw, state: torch.Tensor, agent_ft: torch.Tensor, exact: bool = Fa
     """One ``World.step()`` of ``hw`` (a ``HipWorld``) from the packed ``state`` [E, 6, ld] / ``agent_ft`` [A, 3, ld] ->
     ``(state', agent_ft')``, fresh tensors that autograd differentiates with respect to both inputs.  ``agent_ft'`` is
     the force buffer as the step leaves it (clamped where agents have max_f / f_range / max_t / t_range).  ``exact``:
-    as ``HipWorld.step`` (for the worlds served here - sphere-sphere pairs only - it changes nothing: such a pair's force
-    is exactly 0 wherever the bounding circles do not overlap)."""
+    as ``HipWorld.step``.  For a world of sphere-sphere pairs only it changes nothing (such a pair's force is exactly 0
+    wherever the bounding circles do not overlap); with a line-sphere or box-sphere pair it raises ``NotImplementedError``."""
     why = hw.vjp_supported()
     if why is not None:
         raise NotImplementedError(why)
+    if exact and has_shape_pairs(hw.spec):
+        raise NotImplementedError(EXACT_REFUSAL)
     return _WorldStep.apply(hw, bool(exact), state, agent_ft)
