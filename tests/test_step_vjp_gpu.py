@@ -121,8 +121,7 @@ def restate(spec, state, ft, margins=None):
                 v = clamp_norm(v, f32(D.max_speed)) if D.flags & A.F_MAX_SPEED else v
                 v = clamp(v, f32(D.v_range)) if D.flags & A.F_V_RANGE else v
                 p = pos[e] + v * dt
-                if spec.x_semidim is not None:
-                    p = torch.stack([clamp(p[0], spec.x_semidim), clamp(p[1], spec.y_semidim)])
+                p = torch.stack([p[i] if m is None else clamp(p[i], m) for i, m in enumerate((spec.x_semidim, spec.y_semidim))])
                 pos[e], vel[e] = p, v
             if D.flags & A.F_ROTATABLE:
                 av[e] = av[e] * drag + Tq[e] / f32(D.inertia) * dt

@@ -57,8 +57,9 @@ def inputs(name, batch):
     return spec, state, ft
 
 
-def shape_forces(spec, state, note):
-    """Force [E, 2, B] and torque [E, B] of the line-sphere and box-sphere pairs, every pair in every environment."""
+def shape_forces(spec, state, note, seen=None):
+    """Force [E, 2, B] and torque [E, B] of the line-sphere and box-sphere pairs, every pair in every environment.  ``seen``: collects
+    per pair (a, b, the box's winning edge, xm, x = (dist_min - dist) / k, the torque on a), each [B]."""
     k, c, ents = f32(spec.contact_margin), f32(spec.collision_force), spec.entities
     F, T = [0 * state[e, 0:2] for e in range(len(ents))], [0 * state[e, 4] for e in range(len(ents))]
 
@@ -69,12 +70,12 @@ def shape_forces(spec, state, note):
         Da, pa, pb, dm = ents[P.a], state[P.a, 0:2], state[P.b, 0:2], f32(np.float32(ents[P.b].radius) + LMD)
         ax, half = [unit(state[P.a, 4]), unit(state[P.a, 4] + HALF_PI)], (f32(Da.length / 2), f32(Da.width / 2))
         if P.type == A.PAIR_LS:
-            cp, kink = segment(pa, ax[0], half[0], pb)
+            (cp, kink), edge = segment(pa, ax[0], half[0], pb), None
         else:  # the closest of the four edges' closest points, the first of equals
             edges = [segment(pa + sg * half[i] * ax[i], ax[1 - i], half[1 - i], pb) for i in (0, 1) for sg in (1.0, -1.0)]
             dist = torch.stack([norm(pb - q) for q, _ in edges])
             pick = lambda ts: torch.stack(ts).gather(0, dist.argmin(0).expand(ts[0].shape)[None])[0]  # noqa: E731
-            cp, kink = pick([e[0] for e in edges]), pick([e[1] for e in edges])
+            cp, kink, edge = pick([e[0] for e in edges]), pick([e[1] for e in edges]), dist.argmin(0)
             # best against the other edges, as a displacement of the sphere; the same point is the same function
             far, low = torch.stack([norm(q - cp) for q, _ in edges]), dist.min(0).values
             note(((dist - low) * 2 * low / far.clamp_min(1e-9)).masked_fill(far < 1e-9, torch.inf).min(0).values, half[1])
@@ -86,7 +87,10 @@ def shape_forces(spec, state, note):
         note(norm(d) - dm, dm)
         f = c * d / norm(d) * (k * torch.logaddexp(torch.zeros_like(d[0]), (dm - norm(d)) / k))
         f = torch.where((norm(d) < 1e-6) | (norm(d) > dm), torch.zeros_like(f), f)  # on the sphere; the opposite on a, at cp
-        F[P.b], F[P.a], T[P.a] = F[P.b] + f, F[P.a] - f, T[P.a] - ((cp - pa)[0] * f[1] - (cp - pa)[1] * f[0])
+        tq = -((cp - pa)[0] * f[1] - (cp - pa)[1] * f[0])
+        F[P.b], F[P.a], T[P.a] = F[P.b] + f, F[P.a] - f, T[P.a] + tq
+        if seen is not None:
+            seen.append((P.a, P.b, edge, xm.detach(), ((dm - norm(d)) / k).detach(), tq.detach()))
     return torch.stack(F), torch.stack(T)
 
 
