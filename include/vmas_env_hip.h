@@ -296,6 +296,20 @@ int vmas_world_step_env_gated(VmasWorld* w, float* state, float* agent_ft, int64
                               const void* post_buffers, void* stream);
 int vmas_world_gated_refused(VmasWorld* w);
 
+/* The checked step in ONE call and TWO launches: vmas_env_validate_begin's check (without its marker launch), the gated
+ * step behind it, and vmas_env_validate_end's wait.  The gated step kernel reports for the check it is gated on: one thread
+ * of it, in front of the tile's first load, writes the flags (if any) and then the sequence number into the host block, so
+ * the host learns the verdict when the step STARTS, as it did from the marker, with one dependent launch less per step.
+ * Steps of two launches report from the first; the second reads the gate as before.  (Football's lane-compacted kernel and
+ * the navigation epilogue's kernels do not report: the call enqueues the marker launch in front of them, as _begin does.)
+ * `err_host` / `err_dev`: both addresses of the block of vmas_host_word_create.  Returns the VMAS_ACTION_ERR_* flags
+ * (0: the step ran; > 0: it did nothing, the gate is re-opened behind it, and the caller calls vmas_world_gated_refused
+ * and raises), or < 0 on an error of the call itself (vmas_last_error): a null world or block, no `ingest`, n_steps != 1,
+ * the exact broad phase in a form that cannot be gated (vmas_world_exact_form > 1), whatever vmas_world_step_env refuses. */
+int vmas_world_step_env_checked(VmasWorld* w, float* state, float* agent_ft, int64_t ld, const VmasStepArgs* args,
+                                const VmasIngestArgs* ingest, uint32_t* err_host, uint32_t* err_dev, int32_t post_kind,
+                                const void* post_desc, const void* post_buffers, int32_t n_steps, void* stream);
+
 /* K consecutive Environment.step() calls in ONE launch: the same results, bit for bit, as
  * `n_steps` vmas_world_step_env launches without resets in between, but the tile of 64 environments stays in LDS from
  * step to step - per step only the actions are read from HBM and the outputs written; the state goes back once, at the

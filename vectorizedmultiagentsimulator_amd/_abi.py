@@ -330,6 +330,7 @@ EXPORTED_SYMBOLS = (
     "vmas_host_word_gate",
     "vmas_world_step_env_gated",
     "vmas_world_gated_refused",
+    "vmas_world_step_env_checked",
     "vmas_balance_post_step",
     "vmas_transport_post_step",
     "vmas_navigation_post_step",
@@ -433,6 +434,10 @@ def load_library() -> C.CDLL:
     if hasattr(lib, "vmas_world_gated_refused"):  # (an A/B against a library of an earlier round: scripts/gpu_run.sh lazy-cost)
         lib.vmas_world_gated_refused.argtypes = [vp]
         lib.vmas_world_gated_refused.restype = C.c_int
+    if hasattr(lib, "vmas_world_step_env_checked"):  # (an older build beside this one, VMAS_HIP_LIB=...: the three-call path)
+        lib.vmas_world_step_env_checked.argtypes = [vp, vp, vp, i64, C.POINTER(StepArgs), C.POINTER(IngestArgs), vp, vp, i32, vp, vp,
+                                                    i32, vp]
+        lib.vmas_world_step_env_checked.restype = C.c_int
     lib.vmas_env_reset_where.argtypes = [C.POINTER(ResetArgs), i32, i32, i32, vp, vp, vp, i64, vp]
     lib.vmas_env_reset_where.restype = C.c_int
     lib.vmas_world_rollout_env.argtypes = [vp, vp, vp, i64, C.POINTER(StepArgs), C.POINTER(IngestArgs), vp, i32, vp, vp, i32, vp]

@@ -450,12 +450,18 @@ class FusedEnvStep:
             if self.validate_actions and self.launch.can_gate(post.kind):
                 # the reference's asserts without an idle queue: the check is enqueued, the step launched GATED on its result
                 # (it does nothing if an action was refused), and only then does the host wait for the check - while the step
-                # is already running behind it
-                seq = ingest.validate_begin()
-                saved = post.save_bound()
-                desc, buffers, result = post.prepare()
-                self.launch.gated(post.kind, desc, buffers)
-                flags = ingest.validate_end(seq)
+                # is already running behind it.  One foreign call and two launches (fused.StepLauncher.checked: the step reports
+                # the check's verdict itself); three calls and a marker launch with a library that lacks the entry
+                if self.launch.can_check():
+                    saved = post.save_bound()
+                    desc, buffers, result = post.prepare()
+                    flags = self.launch.checked(post.kind, desc, buffers)
+                else:
+                    seq = ingest.validate_begin()
+                    saved = post.save_bound()
+                    desc, buffers, result = post.prepare()
+                    self.launch.gated(post.kind, desc, buffers)
+                    flags = ingest.validate_end(seq)
                 if flags:
                     self.launch.refused()
                     post.restore_bound(saved)  # (the scenario keeps the previous step's pos_rew ...: it saw nothing of this one)

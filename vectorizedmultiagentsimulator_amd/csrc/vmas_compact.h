@@ -135,6 +135,10 @@ __attribute__((amdgpu_waves_per_eu((PLAIN == 2 && OWN == 2 && ENV != ENV_FOOTBAL
                                                                         float* __restrict__ agent_ft, long ld, int batch,
                                                                         int padded, DevStepArgs args_in, const EnvArgs E) {
   if constexpr (ENV != ENV_NONE) {  // a gated launch behind a validation that raised flags: not a single load or store
+    // (the gate alone, no report of the verdict: with env_gate_report here - in any shape tried - hipcc 7.2 stops on the
+    //  football lazy instantiation <ENV_FOOTBALL, DevEnv, 4, 2> with "Illegal instruction detected: Operand has incorrect
+    //  register class, V_CMP_NE_U32_e32 0, $src_shared_base".  The host keeps the marker launch in front of this kernel:
+    //  step_impl, vmas_hip.hip)
     if (env_gate_closed(E)) return;
   }
   DevStepArgs args = args_in;

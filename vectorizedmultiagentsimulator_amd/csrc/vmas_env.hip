@@ -395,9 +395,14 @@ int vmas_env_ingest_actions(const VmasIngestArgs* args, int32_t batch, const flo
 }
 
 // The flag block (pinned, mapped, coherent host memory, 64 bytes): word 0 the VMAS_ACTION_ERR_* flags, word 1 the sequence
-// number of the last validation that has completed (written by mark_done_kernel), word 2 the host's launch counter, bytes
-// 16..23 the address of the GATE word - one uint32 in DEVICE memory that the validation's ingest kernel ORs its flags into and
-// a gated step launch (vmas_world_step_env_gated) reads when it starts.
+// number of the last validation that has completed, word 2 the host's launch counter, bytes 16..23 the address of the GATE
+// word - one uint32 in DEVICE memory that the validation's ingest kernel ORs its flags into and a gated step launch
+// (vmas_world_step_env_gated / _checked) reads when it starts.  Who writes words 0 and 1:
+//   vmas_world_step_env_checked: the gated step launch itself, one thread in front of its first load (env_gate_report,
+//     vmas_step_types.h) - the chain on the stream is check -> step (balance, transport, steps without an epilogue; in front
+//     of the lane-compacted kernel and navigation's kernels the call enqueues mark_done_kernel: launch_marker);
+//   vmas_env_validate_begin (the two-call form, and the blocking check vmas_env_validate_actions of the steps that cannot
+//     be gated): mark_done_kernel, a one-thread launch behind the check - check -> marker [-> step].
 static uint32_t* gate_of(const uint32_t* host) {
   uint32_t* g = nullptr;
   memcpy(&g, host + 4, sizeof(g));
@@ -437,17 +442,24 @@ void vmas_host_word_destroy(uint32_t* host) {
 
 uint32_t* vmas_host_word_gate(uint32_t* host) { return host ? gate_of(host) : nullptr; }
 
+// The check of a validation (arguments checked by the caller): the next sequence number, and the ingest-only launch ORing
+// its flags into the block's gate.
+static uint32_t launch_check(const VmasIngestArgs* args, int32_t batch, const float* state, float* agent_ft, int64_t ld,
+                             uint32_t* err_host, void* stream) {
+  const uint32_t seq = (++err_host[2]) & 0x3fffffffu;
+  if (args->n_agents + args->n_scripts > 0)
+    hipLaunchKernelGGL(ingest_kernel, dim3((batch + 255) / 256, args->n_agents + args->n_scripts), dim3(256), 0,
+                       (hipStream_t)stream, *args, batch, state, agent_ft, (long)ld, gate_of(err_host));
+  return seq;
+}
+
 int vmas_env_validate_begin(const VmasIngestArgs* args, int32_t batch, const float* state, float* agent_ft, int64_t ld,
                             uint32_t* err_host, uint32_t* err_dev, void* stream) {
   if (!err_host || !err_dev) return host_fail("vmas_env_validate_begin: needs the flag word of vmas_host_word_create");
   if (check_ingest_args(args, batch, agent_ft, ld)) return -1;
   if (args->n_scripts > 0 && !state) return host_fail("vmas_env_validate_begin: agent scripts need the world state");
-  uint32_t* gate = gate_of(err_host);
-  const uint32_t seq = (++err_host[2]) & 0x3fffffffu;
-  if (args->n_agents + args->n_scripts > 0)
-    hipLaunchKernelGGL(ingest_kernel, dim3((batch + 255) / 256, args->n_agents + args->n_scripts), dim3(256), 0,
-                       (hipStream_t)stream, *args, batch, state, agent_ft, (long)ld, gate);
-  hipLaunchKernelGGL(mark_done_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, gate, err_dev, err_dev + 1, seq);
+  const uint32_t seq = launch_check(args, batch, state, agent_ft, ld, err_host, stream);
+  hipLaunchKernelGGL(mark_done_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, gate_of(err_host), err_dev, err_dev + 1, seq);
   if (check_launch("vmas_env_validate_begin")) return -1;
   return (int)seq;
 }
@@ -484,6 +496,32 @@ int vmas_env_validate_actions(const VmasIngestArgs* args, int32_t batch, const f
   if (seq < 0) return -1;
   return vmas_env_validate_end(err_host, seq, stream);
 }
+
+}  // extern "C"
+namespace vmas {
+// The halves of vmas_world_step_env_checked (vmas_hip.hip) that live with the flag block.  `checked_begin`: what
+// vmas_env_validate_begin enqueues WITHOUT its marker launch - the gated step launched behind it reports (env_gate_report).
+int checked_begin(const VmasIngestArgs* args, int32_t batch, const float* state, float* agent_ft, int64_t ld, uint32_t* err_host,
+                  void* stream, uint32_t* seq) {
+  if (check_ingest_args(args, batch, agent_ft, ld)) return -1;
+  if (args->n_scripts > 0 && !state) return host_fail("vmas_world_step_env_checked: agent scripts need the world state");
+  *seq = launch_check(args, batch, state, agent_ft, ld, err_host, stream);
+  return check_launch("vmas_world_step_env_checked");
+}
+// the marker launch by itself: for a gated step kernel that does not report (the lane-compacted kernel, vmas_hip.hip step_impl)
+int launch_marker(const uint32_t* gate, uint32_t* err_dev, uint32_t seq, void* stream) {
+  hipLaunchKernelGGL(mark_done_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, gate, err_dev, err_dev + 1, seq);
+  return check_launch("vmas_world_step_env_checked");
+}
+// The step behind the check could not be launched, so nothing reports: the marker launch does, and the flags and the gate
+// are drained as after any validation (the call fails with the step's message whatever the check found).
+void checked_abandon(uint32_t* err_host, uint32_t* err_dev, uint32_t seq, void* stream) {
+  hipLaunchKernelGGL(mark_done_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, gate_of(err_host), err_dev, err_dev + 1, seq);
+  if (hipGetLastError() != hipSuccess) return;
+  (void)vmas_env_validate_end(err_host, (int32_t)seq, stream);
+}
+}  // namespace vmas
+extern "C" {
 
 // ------------------------------------------------------------------------------------ masked reset
 // Philox4x32-10 (Salmon et al., SC'11): counter-based, so a reset needs no shared stream state.

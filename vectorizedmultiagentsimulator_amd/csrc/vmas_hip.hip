@@ -71,8 +71,12 @@ template <int LEVEL, int ENV, class EnvArgs, int PLAIN>
 __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel(DevWorld W_in, float* __restrict__ state,
                                                                float* __restrict__ agent_ft, long ld, int batch,
                                                                DevStepArgs args_in, const EnvArgs E) {
-  if constexpr (ENV != ENV_NONE) {  // a gated launch behind a validation that raised flags: not a single load or store
+  if constexpr (ENV == ENV_NAVIGATION) {  // a gated launch behind a validation that raised flags: not a single load or store
+    // (the gate alone: the report's two kernel arguments take the navigation shard form from 39 to 54 spilled scalars - the
+    //  host keeps the marker launch in front of this epilogue's kernels: step_impl, vmas_hip.hip)
     if (env_gate_closed(E)) return;
+  } else if constexpr (ENV != ENV_NONE) {  // ... and the check's verdict to the host, by one thread, in front of the first load
+    if (env_gate_report(E)) return;
   }
   DevStepArgs args = args_in;
   DevWorld W = W_in;
@@ -971,6 +975,11 @@ int check_transport_args(const VmasTransportDesc* d, const VmasTransportBuffers*
                          int64_t ld, int n_entities);
 int launch_football_post(const VmasFootballDesc* d, const VmasFootballBuffers* o, int32_t batch, const float* state, int64_t ld,
                          int stp, void* stream, const uint32_t* gate);
+// vmas_world_step_env_checked's check launch and what it does when the step behind it could not be launched (vmas_env.hip)
+int checked_begin(const VmasIngestArgs* args, int32_t batch, const float* state, float* agent_ft, int64_t ld, uint32_t* err_host,
+                  void* stream, uint32_t* seq);
+void checked_abandon(uint32_t* err_host, uint32_t* err_dev, uint32_t seq, void* stream);
+int launch_marker(const uint32_t* gate, uint32_t* err_dev, uint32_t seq, void* stream);  // mark_done_kernel
 }
 #define HIP_TRY(x)                                                                      \
   do {                                                                                  \
@@ -2597,7 +2606,8 @@ int vmas_world_rollout(VmasWorld* w, float* state, float* agent_ft, int64_t ld, 
 
 static int step_env_impl(VmasWorld* w, float* state, float* agent_ft, int64_t ld, const VmasStepArgs* args,
                          const VmasIngestArgs* ingest, uint32_t* err_flags, int32_t post_kind, const void* post_desc,
-                         const void* post_buffers, int32_t n_steps, void* stream, int gated = 0);
+                         const void* post_buffers, int32_t n_steps, void* stream, int gated = 0, uint32_t* report = nullptr,
+                         uint32_t report_seq = 0);
 
 // LDS (bytes) a fused epilogue needs behind the tile: `fixed` + `per_wave` floats for each of min(waves per tile, cap)
 // waves.  If the tile plus that does not fit the CU, the shared pair rows are given up once (the schedule is rebuilt).
@@ -2677,6 +2687,29 @@ int vmas_world_step_env_gated(VmasWorld* w, float* state, float* agent_ft, int64
   return step_env_impl(w, state, agent_ft, ld, args, ingest, gate, post_kind, post_desc, post_buffers, 1, stream, 1);
 }
 
+int vmas_world_step_env_checked(VmasWorld* w, float* state, float* agent_ft, int64_t ld, const VmasStepArgs* args,
+                                const VmasIngestArgs* ingest, uint32_t* err_host, uint32_t* err_dev, int32_t post_kind,
+                                const void* post_desc, const void* post_buffers, int32_t n_steps, void* stream) {
+  if (!w) return fail("vmas_world_step_env_checked: null world");
+  if (!err_host || !err_dev) return fail("vmas_world_step_env_checked: needs the flag word of vmas_host_word_create");
+  if (n_steps != 1) return fail("vmas_world_step_env_checked: single steps only, got n_steps %d", n_steps);
+  if (!ingest) return fail("vmas_world_step_env_checked: the actions to check come through `ingest`");
+  if (w->host_only) return fail("vmas_world_step_env_checked: a planning world (device -1) cannot be stepped");
+  // (refused here, in front of the check's launch, not by the step behind it)
+  if (args && args->exact_broad_phase && exact_form(w, stream_capturing((hipStream_t)stream)) > EXACT_LAZY)
+    return fail("vmas_world_step_env_checked: this world's exact broad phase carries a grid barrier / several launches here and "
+                "cannot be gated (vmas_world_exact_form): check with vmas_env_validate_actions, then step");
+  uint32_t* gate = vmas_host_word_gate(err_host);
+  uint32_t seq = 0;
+  if (vmas::checked_begin(ingest, w->batch, state, agent_ft, ld, err_host, stream, &seq)) return -1;
+  if (step_env_impl(w, state, agent_ft, ld, args, ingest, gate, post_kind, post_desc, post_buffers, 1, stream, 1, err_dev, seq)) {
+    vmas::checked_abandon(err_host, err_dev, seq, stream);
+    return -1;
+  }
+  // the step's first instructions write `seq`: polled while the step runs; on flags the gate is re-opened behind the step
+  return vmas_env_validate_end(err_host, (int32_t)seq, stream);
+}
+
 int vmas_world_gated_refused(VmasWorld* w) {
   if (!w) return fail("vmas_world_gated_refused: null world");
   w->nav_seq -= w->gated_nav_seq;
@@ -2697,7 +2730,8 @@ int vmas_world_rollout_env(VmasWorld* w, float* state, float* agent_ft, int64_t 
 
 static int step_env_impl(VmasWorld* w, float* state, float* agent_ft, int64_t ld, const VmasStepArgs* args,
                          const VmasIngestArgs* ingest, uint32_t* err_flags, int32_t post_kind, const void* post_desc,
-                         const void* post_buffers, int32_t n_steps, void* stream, int gated) {
+                         const void* post_buffers, int32_t n_steps, void* stream, int gated, uint32_t* report,
+                         uint32_t report_seq) {
   if (!w) return fail("vmas_world_step_env: null world");
   if (gated) {
     // A gated launch must be the WHOLE step: kinds whose step can be more than one launch (football beyond one tile per CU,
@@ -2723,6 +2757,8 @@ static int step_env_impl(VmasWorld* w, float* state, float* agent_ft, int64_t ld
   env.ablate = env_ablate;
   env.err_flags = err_flags;
   env.gated = gated ? 1 : 0;
+  env.report = gated ? report : nullptr;  // (the FIRST launch of the step reports: every form launches its step kernel first)
+  env.report_seq = report_seq;
   for (int a = 0; a < VMAS_ENV_MAX_AGENTS; ++a) env.script_of_agent[a] = -1;
   if (ingest) {
     if (vmas::check_ingest_args(ingest, w->batch, agent_ft, ld)) return -1;
@@ -2962,6 +2998,13 @@ static int step_impl(VmasWorld* w, float* state, float* agent_ft, int64_t ld, co
     }
     if (env_kind == ENV_NONE) return launch_physics(w, S, state, agent_ft, ld, a, s);
     const bool cp = compact_on(w) && !a.joint_fixed_rot && !(ABLATE(a) & 0xff) && !ABLATE(*env) && compact_takes(a);
+    if (env->report != nullptr && (env_kind == ENV_NAVIGATION || (cp && (env_kind == ENV_INGEST || env_kind == ENV_FOOTBALL)))) {
+      // the lane-compacted kernel (vmas_compact.h) and the navigation epilogue's kernels read the gate but do not report: the
+      // one-thread marker launch in front of them does, as in the two-call form - check -> marker -> step for football and
+      // navigation
+      if (vmas::launch_marker(env->err_flags, env->report, env->report_seq, s)) return -1;
+      env->report = nullptr;
+    }
     if (env_kind == ENV_INGEST && cp) return launch_compact(w, ENV_INGEST, state, agent_ft, ld, a, env, 0, s, w->batch, ld);
     if (env_kind == ENV_FOOTBALL) {
       if (!cp) return fail("vmas_world_step_env: the football epilogue runs behind the compacted step kernel, which this world / "

@@ -105,6 +105,11 @@ struct DevEnv {
   // for it), so the prologue reads its slot with one kernarg fetch, no indirection.  Scripts: agent -> script or -1.
   int8_t script_of_agent[VMAS_ENV_MAX_AGENTS];
   uint32_t* err_flags;
+  // vmas_world_step_env_checked: the gated launch is its validation's messenger as well - the device address of the host
+  // flag block (word 0 the flags, word 1 the sequence number: vmas_env.hip) and this validation's number.  NULL: no report
+  // (a marker launch in front of this one made it, or nobody waits for one)
+  uint32_t* report;
+  uint32_t report_seq;
   unsigned long long* trace;  // profiling only (VMAS_TRACE=2): per-wave s_memtime stamps of the world-specialised kernel
   VmasIngestArgs ingest;
   union {
@@ -115,12 +120,34 @@ struct DevEnv {
   };
 };
 struct NoEnv {};
-// block-uniform: every thread of the launch reads the same word (a scalar load; the validation's launch in front of this one
-// on the same stream wrote it - kernel boundaries make it visible)
-__device__ __forceinline__ bool env_gate_closed(const DevEnv& E) {
+// Is the gate of a gated launch shut?  Block-uniform: every thread of the launch reads the same word (the validation's launch
+// in front of this one on the same stream wrote it - kernel boundaries make it visible).
+// And the validation's verdict to the host (E.report), by ONE thread of the launch and in front of the tile's first load:
+// the check this launch is gated on has completed when it starts, so the launch itself does what a one-thread marker
+// launch between the two would - a dependent launch less per checked step.  Gate shut: the flags into host word 0, then
+// the sequence number into word 1 with release order (the host acquires word 1 and must find the flags behind it).  Gate
+// open: the sequence number alone - nothing precedes it, so a relaxed store, and no write-back in front of the tile's work.
+// The host block is uncached, coherent memory: the stores leave at once, not with the kernel's end.
+__device__ __forceinline__ bool env_gate_closed(const DevEnv& E) {  // (the gate alone: the lane-compacted kernel, see there)
   return E.gated != 0 && __builtin_amdgcn_readfirstlane((int)*(const volatile uint32_t*)E.err_flags) != 0;
 }
 __device__ __forceinline__ bool env_gate_closed(const NoEnv&) { return false; }
+__device__ __forceinline__ bool env_gate_report(const DevEnv& E) {
+  if (E.gated == 0) return false;
+  const uint32_t f = (uint32_t)__builtin_amdgcn_readfirstlane((int)*(const volatile uint32_t*)E.err_flags);
+  if (E.report != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+    // (a global address, said so: no aperture test of a generic pointer in front of the atomic)
+    auto* host = (__attribute__((address_space(1))) uint32_t*)E.report;
+    if (f != 0u) {
+      __hip_atomic_fetch_or(host, f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+      __hip_atomic_store(host + 1, E.report_seq, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+    } else {
+      __hip_atomic_store(host + 1, E.report_seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    }
+  }
+  return f != 0u;
+}
+__device__ __forceinline__ bool env_gate_report(const NoEnv&) { return false; }
 
 // What a code object compiled at run time (specialize.py) must agree with the library on besides the schedule: the layout of
 // the kernel arguments.  Both sides compute this from THEIR headers - the library when it was built, the specialisation when

@@ -426,12 +426,19 @@ class Environment:
         if self._one_launch:
             self._ingest.prepare(actions)
             if self.validate_actions and self._launch.can_gate(self._post.kind):
-                # the check enqueued, the step launched GATED on its result, the host's wait behind both (fused.StepLauncher.gated)
-                seq = self._ingest.validate_begin()
-                saved = self._post.save_bound()
-                desc, buffers, result = self._post.prepare()
-                self._launch.gated(self._post.kind, desc, buffers)
-                flags = self._ingest.validate_end(seq)
+                # the check enqueued, the step launched GATED on its result, the host's wait behind both: one foreign call and
+                # two launches (fused.StepLauncher.checked - the step reports the check's verdict itself); three calls and the
+                # marker launch between check and step with a library that lacks the entry
+                if self._launch.can_check():
+                    saved = self._post.save_bound()
+                    desc, buffers, result = self._post.prepare()
+                    flags = self._launch.checked(self._post.kind, desc, buffers)
+                else:
+                    seq = self._ingest.validate_begin()
+                    saved = self._post.save_bound()
+                    desc, buffers, result = self._post.prepare()
+                    self._launch.gated(self._post.kind, desc, buffers)
+                    flags = self._ingest.validate_end(seq)
                 if flags:
                     self._launch.refused()
                     self._post.restore_bound(saved)

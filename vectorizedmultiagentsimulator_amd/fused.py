@@ -396,6 +396,9 @@ class StepLauncher:
         self._err = C.c_void_p(self.ingest.err_ptr)
         self._gate = C.c_void_p(self.ingest.gate_ptr)
         self._gated_fn = A.load_library().vmas_world_step_env_gated
+        # (None: a library from before the entry existed, VMAS_HIP_LIB=...: the callers take the three-call path)
+        self._checked_fn = getattr(A.load_library(), "vmas_world_step_env_checked", None)
+        self._err_host = C.c_void_p(self.ingest._err_host_ptr)
         self._dev = self.env.device
 
     def __call__(self, kind: int, desc, buffers, validate: bool):
@@ -404,6 +407,16 @@ class StepLauncher:
             self._bind()
         w._query_cache = None
         args = self._args(w)
+        if desc is not self._cd or buffers is not self._cb:
+            self._cache_refs(desc, buffers)
+        rc = self.fn(self._h, self._st, self._ft, self._ld, args, self._ing, self._err if validate else None, kind,
+                     self._rd, self._rb, _stream(self._dev))
+        if rc != 0:
+            raise VmasHipError(A.last_error())
+
+
+    def _cache_refs(self, desc, buffers):
+        """``byref`` of the descriptor and buffer structs of this call into ``_rd`` / ``_rb``, built once per struct."""
         if desc is not self._cd:  # (the structs persist: their references are built once)
             self._cd = desc
             self._rd = C.byref(desc) if desc is not None else None
@@ -418,11 +431,6 @@ class StepLauncher:
                         self._refs.clear()
                     hit = self._refs[id(buffers)] = (buffers, C.byref(buffers))
                 self._rb = hit[1]
-        rc = self.fn(self._h, self._st, self._ft, self._ld, args, self._ing, self._err if validate else None, kind,
-                     self._rd, self._rb, _stream(self._dev))
-        if rc != 0:
-            raise VmasHipError(A.last_error())
-
 
     def _args(self, w):
         """``VmasStepArgs*`` of this step (None: no optional input).  Without per-environment inputs the struct never changes: ONE
@@ -464,6 +472,29 @@ class StepLauncher:
                             _stream(self._dev))
         if rc != 0:
             raise VmasHipError(A.last_error())
+
+    def can_check(self) -> bool:
+        """Does the loaded library have ``vmas_world_step_env_checked``?"""
+        if self._be is None or self.env.world._backend is not self._be:
+            self._bind()
+        return self._checked_fn is not None
+
+    def checked(self, kind: int, desc, buffers) -> int:
+        """``vmas_world_step_env_checked``: the check, the step gated on it (which reports the check's verdict itself) and the
+        wait for that verdict in ONE foreign call.  Returns the action flags: 0 - the step ran; else it did nothing and the
+        caller calls ``refused()`` and raises.  Marshalled like ``__call__``: cached references, no ctypes object per call."""
+        w = self.env.world
+        if self._be is None or w._backend is not self._be:
+            self._bind()
+        w._query_cache = None
+        args = self._args(w)
+        if desc is not self._cd or buffers is not self._cb:
+            self._cache_refs(desc, buffers)
+        flags = self._checked_fn(self._h, self._st, self._ft, self._ld, args, self._ing, self._err_host, self._err, kind,
+                                 self._rd, self._rb, 1, _stream(self._dev))
+        if flags < 0:
+            raise VmasHipError(A.last_error())
+        return flags
 
     def rollout(self, kind: int, desc, buffers, n_steps: int):
         """``vmas_world_rollout_env``: n_steps Environment.step() calls in one launch."""
