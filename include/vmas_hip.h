@@ -264,7 +264,8 @@ int vmas_world_exact_form(VmasWorld* w);
 int vmas_world_pair_mask(VmasWorld* w, const float* state, int64_t ld, uint32_t* mask, void* stream);
 
 /* Replaces World.cast_rays for a set of sensors (core.py:1662-1786).  Registers
- * the sensor set once ... */
+ * the sensor set once ...  (On a planning world - device -1 - only the host-side description and the plan of the
+ * backward kernel below are recorded; everything that touches the device still fails there.) */
 int vmas_world_set_lidars(VmasWorld* w, const VmasLidarDesc* lidars, int32_t n_lidars);
 /* ... then out[(l * max_rays + r) * ld + env] = measured distance; max_rays is the
  * largest n_rays of the registered set. */
@@ -274,6 +275,25 @@ int vmas_world_cast_rays(VmasWorld* w, const float* state, int64_t ld, float* ou
  * vmas_world_get_lidar_compact: 1 if the next vmas_world_cast_rays takes the compacted form. */
 int vmas_world_set_lidar_compact(VmasWorld* w, int32_t mode);
 int vmas_world_get_lidar_compact(VmasWorld* w);
+
+/* The vector-Jacobian product of World.cast_rays (csrc/vmas_lidar_vjp.hip) for the registered sensor set:
+ * spheres, boxes and lines as targets, any number of sensors per entity.  The plan is made by vmas_world_set_lidars and
+ * released with the sensor set.
+ * vmas_world_cast_rays_vjp_check: 0 if vmas_world_cast_rays_vjp can serve the set; -1 + vmas_last_error() if no sensors
+ * are registered or one sensor's accumulator rows do not fit the compute unit's LDS (with the byte counts).  No GPU work;
+ * works on a planning world.
+ * vmas_world_cast_rays_vjp_plan: the same, and what the planner decided (any pointer may be NULL): the runs the sensors
+ * are processed in, the (sensor, ray chunk) work units, the waves of a 64-environment tile and the tile's LDS bytes. */
+int vmas_world_cast_rays_vjp_check(VmasWorld* w);
+int vmas_world_cast_rays_vjp_plan(VmasWorld* w, int32_t* n_runs, int32_t* n_units, int32_t* n_waves, int64_t* lds_bytes);
+/* VJP of ONE vmas_world_cast_rays(w, state, ld, out, stream).  state [E][6][ld]: the buffer that cast read; g_out
+ * [n_lidars][max_rays][ld]: cotangent of its output (rows r >= n_rays of a sensor and columns >= batch are not read);
+ * g_state [E][6][ld]: passed ZERO-FILLED, the kernel stores fields 0, 1 (position) and 4 (rotation) of every entity that
+ * carries a sensor or is seen by one, columns < batch, and touches nothing else.  A ray's cotangent goes to the one target
+ * that gave its minimum (torch.min's rule) and nowhere when the minimum is max_range; the hit / miss decisions are the
+ * forward's.  fp32, no float atomics: two runs on the same inputs are bitwise equal.  Asynchronous on `stream`, allocates
+ * nothing, never waits. */
+int vmas_world_cast_rays_vjp(VmasWorld* w, const float* state, int64_t ld, const float* g_out, float* g_state, void* stream);
 
 /* Scenario-side geometric queries (World.get_distance core.py:1822-1905,
  * World.is_overlapping core.py:1907-1969) evaluated for a registered list of entity pairs in

@@ -295,6 +295,9 @@ EXPORTED_SYMBOLS = (
     "vmas_world_cast_rays",
     "vmas_world_set_lidar_compact",
     "vmas_world_get_lidar_compact",
+    "vmas_world_cast_rays_vjp_check",
+    "vmas_world_cast_rays_vjp_plan",
+    "vmas_world_cast_rays_vjp",
     "vmas_world_set_queries",
     "vmas_world_run_queries",
     "vmas_world_set_lanes_per_env",
@@ -378,6 +381,12 @@ def load_library() -> C.CDLL:
     lib.vmas_world_set_lidars.restype = C.c_int
     lib.vmas_world_cast_rays.argtypes = [vp, vp, i64, vp, vp]
     lib.vmas_world_cast_rays.restype = C.c_int
+    lib.vmas_world_cast_rays_vjp_check.argtypes = [vp]
+    lib.vmas_world_cast_rays_vjp_check.restype = C.c_int
+    lib.vmas_world_cast_rays_vjp_plan.argtypes = [vp, C.POINTER(i32), C.POINTER(i32), C.POINTER(i32), C.POINTER(i64)]
+    lib.vmas_world_cast_rays_vjp_plan.restype = C.c_int
+    lib.vmas_world_cast_rays_vjp.argtypes = [vp, vp, i64, vp, vp, vp]
+    lib.vmas_world_cast_rays_vjp.restype = C.c_int
     lib.vmas_world_set_queries.argtypes = [vp, C.POINTER(Query), i32]
     lib.vmas_world_set_queries.restype = C.c_int
     lib.vmas_world_run_queries.argtypes = [vp, vp, i64, vp, vp]

@@ -455,13 +455,48 @@ class HipWorld:
     def lidar_compact(self) -> bool:
         return bool(self.lib.vmas_world_get_lidar_compact(self._h))
 
-    def cast_rays(self, stream=None) -> torch.Tensor:
-        """World.cast_rays for every registered Lidar: [n_lidars, max_rays, ld]."""
+    def cast_rays(self, state: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, stream=None) -> torch.Tensor:
+        """World.cast_rays for every registered Lidar: [n_lidars, max_rays, ld].  ``state`` / ``out``: a packed state to
+        cast in place of the adopted one, and a tensor to cast into in place of the re-used output buffer
+        (differentiable.py casts into fresh tensors)."""
         if self._lidar_out is None:
             raise VmasHipError("this world has no Lidar sensors")
-        rc = self.lib.vmas_world_cast_rays(
-            self._h, self._dptr(self.state), self.ld, self._dptr(self._lidar_out), self._stream(stream)
-        )
+        state = self.state if state is None else self._packed_like(state, self.state, "state")
+        out = self._lidar_out if out is None else self._packed_like(out, self._lidar_out, "out")
+        rc = self.lib.vmas_world_cast_rays(self._h, self._dptr(state), self.ld, self._dptr(out), self._stream(stream))
         if rc != 0:
             raise VmasHipError(A.last_error())
-        return self._lidar_out
+        return out
+
+    # ------------------------------------------------------------------ backward of World.cast_rays
+    def lidar_vjp_supported(self) -> Optional[str]:
+        """None if ``cast_rays_vjp`` serves the registered sensor set, else why not (include/vmas_hip.h,
+        vmas_world_cast_rays_vjp_check: no sensors, or a sensor whose accumulator rows do not fit the LDS)."""
+        why = getattr(self, "_lidar_vjp_why", False)
+        if why is False:
+            why = self._lidar_vjp_why = None if self.lib.vmas_world_cast_rays_vjp_check(self._h) == 0 else A.last_error()
+        return why
+
+    def lidar_vjp_plan(self) -> dict:
+        """What the planner of the LIDAR's backward kernel decided: runs, work units, waves per tile, LDS bytes of a tile."""
+        runs, units, waves, lds = C.c_int32(), C.c_int32(), C.c_int32(), C.c_int64()
+        if self.lib.vmas_world_cast_rays_vjp_plan(self._h, C.byref(runs), C.byref(units), C.byref(waves), C.byref(lds)) != 0:
+            raise VmasHipError(A.last_error())
+        return dict(runs=runs.value, units=units.value, waves=waves.value, lds_bytes=lds.value)
+
+    def cast_rays_vjp(self, state: torch.Tensor, g_out: torch.Tensor, stream=None) -> torch.Tensor:
+        """Vector-Jacobian product of ONE ``cast_rays(state)`` in one launch of the backward kernel (csrc/vmas_lidar_vjp.hip).
+        ``state`` [E, 6, ld]: the packed state that cast read; ``g_out`` [n_lidars, max_rays, ld]: cotangent of its result.
+        Returns ``g_state`` [E, 6, ld]: non-zero only in the position and rotation rows of entities that carry a sensor or
+        are seen by one, zero in the padding columns.  Asynchronous on the (current) stream."""
+        why = self.lidar_vjp_supported()
+        if why is not None:
+            raise VmasHipError(why)
+        state = self._packed_like(state, self.state, "state")
+        g_out = self._packed_like(g_out.contiguous(), self._lidar_out, "g_out")
+        g_state = torch.zeros_like(self.state)
+        rc = self.lib.vmas_world_cast_rays_vjp(self._h, self._dptr(state), self.ld, self._dptr(g_out), self._dptr(g_state),
+                                               self._stream(stream))
+        if rc != 0:
+            raise VmasHipError(A.last_error())
+        return g_state

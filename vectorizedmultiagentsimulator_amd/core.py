@@ -944,6 +944,9 @@ class World:
 
     def cast_rays_all(self) -> Tensor:
         """All Lidar sensors of all agents at once: [n_lidars, max_rays, ld]."""
-        if self.grad_enabled:
-            raise NotImplementedError("the LIDAR kernel has no backward: grad_enabled worlds cannot cast rays")
-        return self._get_backend().cast_rays()
+        be = self._get_backend()
+        if self.grad_enabled:  # on the tape: a fresh tensor per cast, the backward is one launch (differentiable.cast_rays)
+            from .differentiable import cast_rays
+
+            return cast_rays(be, self._state)
+        return be.cast_rays()

@@ -1,7 +1,7 @@
 #!/bin/bash
 # Build libvmas_hip.so for gfx950 (MI355X).  hipcc cross-compiles without a GPU.
 #   -ffp-contract=off : reference operation order, no silent FMA fusion (parity)
-# The four translation units compile side by side (the step kernel's template instantiations dominate), then link.
+# The five translation units compile side by side (the step kernel's template instantiations dominate), then link.
 # Objects are cached under .obj/ (git-ignored) keyed by a hash of the unit's sources and flags: a change to the
 # lane-compacted kernel recompiles in seconds instead of minutes.  VMAS_BUILD_FORCE=1 ignores the cache.
 set -euo pipefail
@@ -13,10 +13,11 @@ OBJ=.obj
 mkdir -p "$OBJ"
 COMMON="vmas_device.h vmas_env_device.h ../../include/vmas_hip.h ../../include/vmas_env_hip.h ../../include/vmas_debug_hip.h"
 declare -A DEPS=(
-  [vmas_hip]="vmas_hip.hip vmas_step_device.h vmas_step_types.h vmas_spec_gen.h vmas_spec_kernel.h vmas_compact.h vmas_vjp.h $COMMON"
+  [vmas_hip]="vmas_hip.hip vmas_step_device.h vmas_step_types.h vmas_spec_gen.h vmas_spec_kernel.h vmas_compact.h vmas_vjp.h vmas_lidar_vjp.h $COMMON"
   [vmas_env]="vmas_env.hip $COMMON"
   [vmas_compact]="vmas_compact.hip vmas_compact.h vmas_step_types.h $COMMON"
   [vmas_vjp]="vmas_vjp.hip vmas_vjp.h vmas_device.h ../../include/vmas_hip.h"
+  [vmas_lidar_vjp]="vmas_lidar_vjp.hip vmas_lidar_vjp.h vmas_device.h"
 )
 # (the backward kernel is built without packed fp32 arithmetic: its 2-vector sums stay two scalar operations)
 declare -A UNIT_FLAGS=(
@@ -24,7 +25,7 @@ declare -A UNIT_FLAGS=(
 )
 pids=()
 objs=()
-for unit in vmas_hip vmas_env vmas_compact vmas_vjp; do
+for unit in vmas_hip vmas_env vmas_compact vmas_vjp vmas_lidar_vjp; do
   UF="${UNIT_FLAGS[$unit]:-}"
   key=$( (echo "$FLAGS $UF"; "$HIPCC" --version | head -2; cat ${DEPS[$unit]}) | sha256sum | cut -c1-16)
   o="$OBJ/$unit.$key.o"
@@ -39,7 +40,7 @@ done
 for p in "${pids[@]:-}"; do [ -n "$p" ] && wait "$p"; done
 # the build id (vmas_build_id): a digest of everything the library is built from, in a translation unit of its own - part of
 # the key of the run-time specialisations' on-disk cache (specialize.py)
-BUILD_ID=$( (echo "$FLAGS"; "$HIPCC" --version | head -2; cat vmas_hip.hip vmas_env.hip vmas_compact.hip vmas_vjp.hip *.h ../../include/*.h) | sha256sum | cut -c1-32)
+BUILD_ID=$( (echo "$FLAGS"; "$HIPCC" --version | head -2; cat vmas_hip.hip vmas_env.hip vmas_compact.hip vmas_vjp.hip vmas_lidar_vjp.hip *.h ../../include/*.h) | sha256sum | cut -c1-32)
 printf 'extern "C" { extern const char vmas_build_id_string[]; const char vmas_build_id_string[] = "%s"; }\n' "$BUILD_ID" > "$OBJ/build_id.$BUILD_ID.cpp"
 g++ -O1 -fPIC -c "$OBJ/build_id.$BUILD_ID.cpp" -o "$OBJ/build_id.$BUILD_ID.o"
 # (-z defs: a symbol one unit declares and no unit defines fails HERE, not at dlopen on the GPU box)

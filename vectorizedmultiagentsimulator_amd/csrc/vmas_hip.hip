@@ -54,6 +54,7 @@
 #include "../../include/vmas_hip.h"
 #include "../../include/vmas_debug_hip.h"
 #include "vmas_step_types.h"
+#include "vmas_lidar_vjp.h"
 #include "vmas_vjp.h"
 
 #include "vmas_step_device.h"
@@ -1057,6 +1058,7 @@ struct VmasWorld {
   bool host_only = false;  // a PLANNING world (device_id -1): schedules are built on the host, nothing is uploaded or launched
   bool use_spec = true;    // launch the world-specialised kernel when the schedule matches one (vmas_world_set_specialized)
   vmas::vjp::Plan vjp;     // the backward kernel of World.step (vmas_vjp.hip): its table and tile layout, or why it refuses this world
+  vmas::lidar_vjp::Plan lidar_vjp;  // the backward kernel of World.cast_rays (vmas_lidar_vjp.hip), made by vmas_world_set_lidars
   static constexpr int MAX_QUEUES = 4;
   hipStream_t side[MAX_QUEUES - 1] = {nullptr, nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[MAX_QUEUES - 1] = {nullptr, nullptr, nullptr};
@@ -2417,6 +2419,7 @@ void vmas_world_destroy(VmasWorld* w) {
   (void)hipFree(w->cp.d_blob); (void)hipFree(w->cp.d_trig);
   (void)hipFree(w->d_mpairs); (void)hipFree(w->d_trace);
   vmas::vjp::release(&w->vjp);
+  vmas::lidar_vjp::release(&w->lidar_vjp);
   (void)hipFree(w->d_lidars); (void)hipFree(w->d_targets); (void)hipFree(w->d_angles); (void)hipFree(w->d_queries);
   (void)hipFree(w->d_angles_cs);
   delete w;
@@ -3215,13 +3218,17 @@ int vmas_world_pair_mask(VmasWorld* w, const float* state, int64_t ld, uint32_t*
   return 0;
 }
 
+// (a planning world - device -1 - records the host-side description and the backward plan only: nothing is uploaded)
 int vmas_world_set_lidars(VmasWorld* w, const VmasLidarDesc* lidars, int32_t n) {
-  if (w && w->host_only) return fail("vmas_world_set_lidars: a planning world (device -1) has no device side");
   if (!w || (n > 0 && !lidars)) return fail("vmas_world_set_lidars: null argument");
-  HIP_TRY(hipSetDevice(w->device));
-  (void)hipFree(w->d_lidars); (void)hipFree(w->d_targets); (void)hipFree(w->d_angles); (void)hipFree(w->d_angles_cs);
+  if (!w->host_only) {
+    HIP_TRY(hipSetDevice(w->device));
+    (void)hipFree(w->d_lidars); (void)hipFree(w->d_targets); (void)hipFree(w->d_angles); (void)hipFree(w->d_angles_cs);
+  }
   w->d_lidars = nullptr; w->d_targets = nullptr; w->d_angles = nullptr; w->d_angles_cs = nullptr;
   w->n_lidars = 0; w->max_rays = 0;
+  vmas::lidar_vjp::release(&w->lidar_vjp);
+  w->lidar_vjp = vmas::lidar_vjp::Plan{};
   w->h_lidars.clear();
   w->h_targets.clear();
   if (n <= 0) return 0;
@@ -3242,6 +3249,20 @@ int vmas_world_set_lidars(VmasWorld* w, const VmasLidarDesc* lidars, int32_t n) 
     for (int r = 0; r < L.n_rays; ++r) da.push_back(L.angles[r]);
     if (L.n_rays > w->max_rays) w->max_rays = L.n_rays;
   }
+  {  // the backward plan (vmas_lidar_vjp.hip): host work only
+    std::vector<vmas::lidar_vjp::Sensor> vs;
+    std::vector<vmas::lidar_vjp::Target> vt;
+    for (const DevLidar& L : dl) vs.push_back({L.entity, L.n_rays, L.n_targets, L.target_off, L.angle_off, L.max_range, L.half_range});
+    for (const DevTarget& T : dt) vt.push_back({T.entity, T.shape, T.length, T.width, T.radius});
+    vmas::lidar_vjp::make_plan(vs.data(), n, vt.data(), da.data(), w->base.nE, &w->lidar_vjp);
+  }
+  if (w->host_only) {
+    w->h_lidars = dl;
+    w->h_targets = dt;
+    w->n_lidars = n;
+    return 0;
+  }
+  if (w->lidar_vjp.ok && vmas::lidar_vjp::upload(&w->lidar_vjp)) return -1;
   HIP_TRY(upload(&w->d_lidars, dl));
   HIP_TRY(upload(&w->d_targets, dt));
   HIP_TRY(upload(&w->d_angles, da));
@@ -3398,6 +3419,32 @@ int vmas_world_cast_rays(VmasWorld* w, const float* state, int64_t ld, float* ou
 #undef LAUNCH_LIDAR
   HIP_TRY(hipGetLastError());
   return 0;
+}
+
+int vmas_world_cast_rays_vjp_check(VmasWorld* w) {
+  if (!w) return fail("vmas_world_cast_rays_vjp_check: null world");
+  if (w->n_lidars <= 0) return fail("vmas_world_cast_rays_vjp: no sensors registered (vmas_world_set_lidars)");
+  if (!w->lidar_vjp.ok) return fail("vmas_world_cast_rays_vjp: %s", w->lidar_vjp.why);
+  return 0;
+}
+
+int vmas_world_cast_rays_vjp_plan(VmasWorld* w, int32_t* n_runs, int32_t* n_units, int32_t* n_waves, int64_t* lds_bytes) {
+  if (vmas_world_cast_rays_vjp_check(w)) return -1;
+  if (n_runs) *n_runs = w->lidar_vjp.n_runs;
+  if (n_units) *n_units = w->lidar_vjp.n_units;
+  if (n_waves) *n_waves = w->lidar_vjp.nw;
+  if (lds_bytes) *lds_bytes = (int64_t)w->lidar_vjp.lds_bytes;
+  return 0;
+}
+
+int vmas_world_cast_rays_vjp(VmasWorld* w, const float* state, int64_t ld, const float* g_out, float* g_state, void* stream) {
+  if (!w) return fail("vmas_world_cast_rays_vjp: null world");
+  if (!state || !g_out || !g_state) return fail("vmas_world_cast_rays_vjp: null buffer");
+  if (ld < w->batch) return fail("vmas_world_cast_rays_vjp: ld (%lld) < batch (%d)", (long long)ld, w->batch);
+  if (vmas_world_cast_rays_vjp_check(w)) return -1;
+  if (w->host_only) return fail("vmas_world_cast_rays_vjp: a planning world (device -1) has no device to launch on");
+  return vmas::lidar_vjp::launch(w->lidar_vjp, w->device, w->batch, w->d_angles_cs, state, (long)ld, g_out, g_state,
+                                 (hipStream_t)stream);
 }
 
 }  // extern "C"

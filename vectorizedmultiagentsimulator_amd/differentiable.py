@@ -8,6 +8,9 @@ With a line-sphere or box-sphere pair the step that is differentiated is the per
 a line's tip or a box's corner such a pair's force is non-zero where the bounding circles do not overlap, and there the
 reference's batch-global rule depends on the other environments of the batch, which a backward without communication
 between tiles cannot reproduce.  ``exact=True`` is refused for these worlds.
+
+``World.cast_rays`` is on the tape the same way (``cast_rays`` below): the forward is the LIDAR kernel, the backward ONE
+launch of csrc/vmas_lidar_vjp.hip through ``HipWorld.cast_rays_vjp``.
 """
 from __future__ import annotations
 
@@ -71,3 +74,32 @@ def world_step(hw, state: torch.Tensor, agent_ft: torch.Tensor, exact: bool = Fa
     if exact and has_shape_pairs(hw.spec):
         raise NotImplementedError(EXACT_REFUSAL)
     return _WorldStep.apply(hw, bool(exact), state, agent_ft)
+
+
+class _CastRays(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, hw, state):
+        state = state.contiguous()
+        # a fresh tensor per cast: the backend's re-used output buffer would be overwritten under an earlier tape
+        out = torch.zeros(len(hw.spec.lidars), hw.cdesc.max_rays, hw.ld, device=state.device, dtype=torch.float32)
+        hw.cast_rays(state=state, out=out)
+        ctx.hw = hw
+        ctx.save_for_backward(state)
+        return out
+
+    @staticmethod
+    @once_differentiable
+    def backward(ctx, g_out):
+        (state,) = ctx.saved_tensors
+        return None, ctx.hw.cast_rays_vjp(state, g_out)
+
+
+def cast_rays(hw, state: torch.Tensor) -> torch.Tensor:
+    """``World.cast_rays`` for every registered Lidar of ``hw`` (a ``HipWorld``) from the packed ``state`` [E, 6, ld] ->
+    [n_lidars, max_rays, ld], a fresh tensor that autograd differentiates with respect to the positions and rotations in
+    ``state``: a ray's cotangent goes to the one target that gave its minimum, and nowhere when nothing is within
+    ``max_range``.  Raises ``NotImplementedError`` with the reason when the sensor set is refused."""
+    why = hw.lidar_vjp_supported()
+    if why is not None:
+        raise NotImplementedError(why)
+    return _CastRays.apply(hw, state)
