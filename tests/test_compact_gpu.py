@@ -69,6 +69,37 @@ def test_compact_kernel_is_bitwise_the_interpreter(name, B):
         assert torch.equal(_bits(a.agent_ft), _bits(b.agent_ft)), f"{name}: clamped forces differ at step {t}"
 
 
+def test_compact_integrator_under_every_clamp_is_bitwise_the_interpreter():
+    """The compacted kernel's integrator with max_speed AND v_range (the eligible fixtures have max_speed at most: the ones
+    with v_range hold line-line pairs): world (b) of test_step_vjp_gpu.py - three agents with every clamp, an immovable
+    sphere, both gravities, x / y bounds, 2 substeps, sphere-sphere pairs only - at two tiles and a tail."""
+    import test_step_vjp_gpu as V
+
+    B = 130
+    spec = V.build_world("b", B).spec
+    state, ft = (t.to(torch.float32).numpy() for t in V.make_inputs(spec, V.WORLDS["b"][0], B, V.WORLDS["b"][1][B], clamps=True))
+    # every clamp is on in some environments and off in others
+    agents = [e for e, D in enumerate(spec.entities) if D.agent_index >= 0]
+    for what, value, limit in (("force norm / max_f", np.hypot(ft[:, 0], ft[:, 1]), V.CLAMPS["max_f"]),
+                               ("|torque| / max_t", np.abs(ft[:, 2]), V.CLAMPS["max_t"]),
+                               ("speed / max_speed", np.hypot(state[agents, 2], state[agents, 3]), V.CLAMPS["max_speed"]),
+                               ("|x| / x_semidim", np.abs(state[agents, 0]), spec.x_semidim),
+                               ("|y| / y_semidim", np.abs(state[agents, 1]), spec.y_semidim)):
+        over = (value > limit).any(axis=0)
+        assert over.any() and not over.all(), f"{what}: over the limit in {int(over.sum())} of {B} environments"
+    a, b = _hip(spec, B), _hip(spec, B)
+    a.set_compact(1)
+    b.set_compact(0)
+    assert a.compact and not b.compact
+    for hw in (a, b):
+        _up(hw, state, ft)
+    for t in range(3):
+        for hw in (a, b):
+            hw.step()
+        assert torch.equal(_bits(a.state), _bits(b.state)), f"state differs at step {t}"
+        assert torch.equal(_bits(a.agent_ft), _bits(b.agent_ft)), f"clamped forces differ at step {t}"
+
+
 @pytest.mark.parametrize("name", ELIGIBLE)
 def test_compact_kernel_matches_the_reference_fixture(name):
     """Teacher-forced on the reference's recorded (state, forces, recorded broad-phase mask) -> state, substep by substep:

@@ -483,7 +483,7 @@ __attribute__((amdgpu_waves_per_eu((PLAIN == 2 && OWN == 2 && ENV != ENV_FOOTBAL
       for (int s = 0; s < OWN; ++s) { F[s] = V(0.f, 0.f); Tq[s] = 0.f; added_a[s] = 0u; added_t[s] = 0u; n_on[s] = 0; n_on_a[s] = 0; }
 
       auto prologue = [&]() {
-      // ---- prologue of every owned entity core.py:1995-2004 (the statements of step_kernel)
+      // ---- prologue of every owned entity core.py:1995-2004
 #pragma unroll
       for (int s = 0; s < OWN; ++s) {
         const int k = wv + s * nw;
@@ -498,8 +498,7 @@ __attribute__((amdgpu_waves_per_eu((PLAIN == 2 && OWN == 2 && ENV != ENV_FOOTBAL
           if (fl & VMAS_F_MOVABLE) {
             v2 f = V(Af[0], Af[ROWF]);
             if (fl & (VMAS_F_MAX_F | VMAS_F_F_RANGE)) {
-              if (fl & VMAS_F_MAX_F) f = clamp_with_norm(f, rdlf(OWv[s], 21));
-              if (fl & VMAS_F_F_RANGE) { const float fr = rdlf(OWv[s], 22); f = V(clamp_t(f.x, fr), clamp_t(f.y, fr)); }
+              f = clamp_action_force(f, fl & VMAS_F_MAX_F, rdlf(OWv[s], 21), fl & VMAS_F_F_RANGE, rdlf(OWv[s], 22)).f;
               Af[0] = f.x; Af[ROWF] = f.y;
               if (last_sub && live) {
                 float* gf = aft + (long)agent_index * 3 * ld + env;
@@ -511,13 +510,7 @@ __attribute__((amdgpu_waves_per_eu((PLAIN == 2 && OWN == 2 && ENV != ENV_FOOTBAL
           if (fl & VMAS_F_ROTATABLE) {
             float t = Af[2 * ROWF];
             if (fl & (VMAS_F_MAX_T | VMAS_F_T_RANGE)) {
-              if (fl & VMAS_F_MAX_T) {
-                const float max_t = rdlf(OWv[s], 23);
-                const float n = fabsf(t);
-                const float nt = (t / n) * max_t;
-                t = n > max_t ? nt : t;
-              }
-              if (fl & VMAS_F_T_RANGE) t = clamp_t(t, rdlf(OWv[s], 24));
+              t = clamp_action_torque(t, fl & VMAS_F_MAX_T, rdlf(OWv[s], 23), fl & VMAS_F_T_RANGE, rdlf(OWv[s], 24)).t;
               Af[2 * ROWF] = t;
               if (last_sub && live) aft[((long)agent_index * 3 + 2) * ld + env] = t;
             }
@@ -820,32 +813,18 @@ __attribute__((amdgpu_waves_per_eu((PLAIN == 2 && OWN == 2 && ENV != ENV_FOOTBAL
         for (int f = 0; f < 6; ++f) es[f] = Es[f * ROWF];
         float* dst = state + (long)e * 6 * ld + env;
         if (fl & VMAS_F_MOVABLE) {
-          v2 vel = V(es[2], es[3]);
-          if (substep == 0) vel = V(vel.x * one_minus_drag, vel.y * one_minus_drag);
-          const rcp_t rm = rcp_of(rdlf(OWv[s], 12));
-          const v2 acc = V(F[s].x / rm, F[s].y / rm);
-          vel = V(vel.x + acc.x * sub_dt, vel.y + acc.y * sub_dt);
-          if (fl & VMAS_F_MAX_SPEED) vel = clamp_with_norm(vel, rdlf(OWv[s], 15));
-          if (fl & VMAS_F_V_RANGE) { const float vr = rdlf(OWv[s], 16); vel = V(clamp_t(vel.x, vr), clamp_t(vel.y, vr)); }
-          v2 np = V(es[0] + vel.x * sub_dt, es[1] + vel.y * sub_dt);
-          if (W.xs == W.xs) np.x = clamp_t(np.x, W.xs);
-          if (W.ys == W.ys) np.y = clamp_t(np.y, W.ys);
+          const v2 vel = integrate_velocity(V(es[2], es[3]), F[s], rdlf(OWv[s], 12), one_minus_drag, substep == 0, sub_dt,
+                                            fl & VMAS_F_MAX_SPEED, rdlf(OWv[s], 15), fl & VMAS_F_V_RANGE, rdlf(OWv[s], 16));
+          const v2 np = integrate_position(V(es[0], es[1]), vel, sub_dt, W.xs, W.ys).p;
           if (last && live) { dst[0] = np.x; dst[ld] = np.y; dst[2 * ld] = vel.x; dst[3 * ld] = vel.y; }
           if (!last || ENV != ENV_NONE) { Es[0] = np.x; Es[ROWF] = np.y; Es[2 * ROWF] = vel.x; Es[3 * ROWF] = vel.y; }
         }
         if (fl & VMAS_F_ROTATABLE) {
-          float av = es[5];
-          if (substep == 0) av = av * one_minus_drag;
-          av = av + (Tq[s] / rdlf(OWv[s], 13)) * sub_dt;
-          const float rot = es[4] + av * sub_dt;
+          const rotation_t rt = integrate_rotation(es[4], es[5], Tq[s], rdlf(OWv[s], 13), one_minus_drag, substep == 0, sub_dt);
+          const float rot = rt.rot, av = rt.av;
           if (last && live) { dst[4 * ld] = rot; dst[5 * ld] = av; }
           if (!last || ENV != ENV_NONE) { Es[4 * ROWF] = rot; Es[5 * ROWF] = av; }
-          if (!last && tr_off >= 0) {
-            float sn, cs;
-            sincosf(rot, &sn, &cs);
-            tile[tr_off] = cs;
-            tile[tr_off + ROWF] = sn;
-          }
+          if (!last && tr_off >= 0) write_trig(tile + tr_off, rot, 2);  // (off_tr: lines only)
         }
       }
       if (!last) __syncthreads();

@@ -154,7 +154,8 @@ VD void box_edges(v2 pos, float c, float s, float c2, float s2, float length, fl
 // physics._get_closest_point_box physics.py:263-295: nearest perimeter point over the four edges, strict < in edge
 // order.  As in closest_seg_box below, an edge is only solved if it can win: |coordinate - edge| in the box frame is a
 // lower bound of the point's distance to that edge, its distance to the perimeter an upper bound of the winner's.
-VD v2 closest_point_box(const seg_t e[4], v2 p) {
+// `edge`: the index of the winning edge (the backward differentiates through that edge alone).
+VD v2 closest_point_box(const seg_t e[4], v2 p, int& edge) {
   const float c = e[2].c, s = e[2].s, hl = e[2].half, hw = e[0].half;
   const float dx = p.x - (e[0].pos.x + e[1].pos.x) * 0.5f, dy = p.y - (e[0].pos.y + e[1].pos.y) * 0.5f;
   const float px = dx * c + dy * s, py = dy * c - dx * s;
@@ -166,6 +167,7 @@ VD v2 closest_point_box(const seg_t e[4], v2 p) {
   const float lb[4] = {fabsf(px - hl), fabsf(px + hl), fabsf(py - hw), fabsf(py + hw)};
   v2 best = V(kInf, kInf);
   float dist = kInf;
+  edge = 0;
 #pragma unroll
   for (int i = 0; i < 4; ++i) {
     if (__any(!(lb[i] > thr))) {
@@ -174,9 +176,14 @@ VD v2 closest_point_box(const seg_t e[4], v2 p) {
       bool cl = d < dist;
       best = cl ? q : best;
       dist = cl ? d : dist;
+      edge = cl ? i : edge;
     }
   }
   return best;
+}
+VD v2 closest_point_box(const seg_t e[4], v2 p) {
+  int edge;
+  return closest_point_box(e, p, edge);
 }
 
 // physics._get_inner_point_box physics.py:13-23
@@ -324,6 +331,99 @@ VD float friction1(float vel, float coeff, float inertia, float sub_dt) {
   float ffc = coeff * inertia;
   float f = -(vel / speed) * min_t(ffc, (fabsf(vel) / sub_dt) * inertia);
   return speed == 0.f ? 0.f : f;
+}
+
+// ------------------------------------------------------------------------------------
+// The entity dynamics of World.step, once: every step kernel and the backward kernel's forward replay call these, which is
+// what makes their clamp decisions the same bits.  Flags and limits arrive as arguments; where they are compile-time
+// constants (the world-specialised kernel) the tests fold.  Each result struct also carries the intermediate values the
+// backward's adjoint needs; a caller that ignores them does not pay for them.
+// ------------------------------------------------------------------------------------
+constexpr int kRow = 64;  // floats per LDS row = environments per tile, in every kernel
+
+// _apply_action_force's clamps core.py:2018-2028; `f1`: behind the norm clamp, `f`: behind the range clamp as well
+struct action_force_t { v2 f1, f; };
+VD action_force_t clamp_action_force(v2 raw, bool has_max_f, float max_f, bool has_f_range, float f_range) {
+  action_force_t r;
+  r.f1 = raw;
+  if (has_max_f) r.f1 = clamp_with_norm(raw, max_f);
+  r.f = r.f1;
+  if (has_f_range) r.f = V(clamp_t(r.f1.x, f_range), clamp_t(r.f1.y, f_range));
+  return r;
+}
+// _apply_action_torque's clamps core.py:2030-2041; `over`: the norm clamp acted, `t1`: behind it, `t`: behind the range clamp
+struct action_torque_t { float t1, t; bool over; };
+VD action_torque_t clamp_action_torque(float raw, bool has_max_t, float max_t, bool has_t_range, float t_range) {
+  action_torque_t r;
+  r.t1 = raw;
+  r.over = false;
+  if (has_max_t) {
+    const float n = fabsf(raw);
+    const float nt = (raw / n) * max_t;
+    r.over = n > max_t;
+    r.t1 = r.over ? nt : raw;
+  }
+  r.t = r.t1;
+  if (has_t_range) r.t = clamp_t(r.t1, t_range);
+  return r;
+}
+
+// _integrate_state core.py:2862-2908.  The linear update in front of its clamps: drag on substep 0 (`drag`), the force over
+// the mass ...
+VD v2 accelerate(v2 vel, v2 F, float mass, float one_minus_drag, bool drag, float sub_dt) {
+  if (drag) vel = V(vel.x * one_minus_drag, vel.y * one_minus_drag);
+  const rcp_t rm = rcp_of(mass);
+  const v2 acc = V(F.x / rm, F.y / rm);
+  return V(vel.x + acc.x * sub_dt, vel.y + acc.y * sub_dt);
+}
+// ... and the clamps: `v1` behind max_speed, `v` (the new velocity) behind v_range
+struct velocity_t { v2 v1, v; };
+VD velocity_t clamp_velocity(v2 pre, bool has_max_speed, float max_speed, bool has_v_range, float v_range) {
+  velocity_t r;
+  r.v1 = pre;
+  if (has_max_speed) r.v1 = clamp_with_norm(pre, max_speed);
+  r.v = r.v1;
+  if (has_v_range) r.v = V(clamp_t(r.v1.x, v_range), clamp_t(r.v1.y, v_range));
+  return r;
+}
+// both: the forward kernels' velocity update (the backward checkpoints the velocity between the two)
+VD v2 integrate_velocity(v2 vel, v2 F, float mass, float one_minus_drag, bool drag, float sub_dt, bool has_max_speed,
+                         float max_speed, bool has_v_range, float v_range) {
+  return clamp_velocity(accelerate(vel, F, mass, one_minus_drag, drag, sub_dt), has_max_speed, max_speed, has_v_range, v_range).v;
+}
+// the position update with the world's bounds (NaN = unbounded); `raw`: in front of the bounds
+struct position_t { v2 raw, p; };
+VD position_t integrate_position(v2 pos, v2 vel, float sub_dt, float xs, float ys) {
+  position_t r;
+  r.raw = V(pos.x + vel.x * sub_dt, pos.y + vel.y * sub_dt);
+  r.p = r.raw;
+  if (xs == xs) r.p.x = clamp_t(r.raw.x, xs);
+  if (ys == ys) r.p.y = clamp_t(r.raw.y, ys);
+  return r;
+}
+// the angular update
+struct rotation_t { float av, rot; };
+VD rotation_t integrate_rotation(float rot, float av, float Tq, float inertia, float one_minus_drag, bool drag, float sub_dt) {
+  if (drag) av = av * one_minus_drag;
+  av = av + (Tq / inertia) * sub_dt;
+  rotation_t r;
+  r.av = av;
+  r.rot = rot + av * sub_dt;
+  return r;
+}
+
+// cos/sin of the rotation(s) the narrow phase needs (physics.py:300-302, 413) into `nt` rows: 2 for a line, 4 for a box
+VD void write_trig(float* tr, float rot, int nt) {
+  float sn, cs;
+  sincosf(rot, &sn, &cs);  // one range reduction for both (ocml), same values as cosf/sinf
+  tr[0 * kRow] = cs;
+  tr[1 * kRow] = sn;
+  if (nt == 4) {
+    const float rot2 = rot + kHalfPi;
+    sincosf(rot2, &sn, &cs);
+    tr[2 * kRow] = cs;
+    tr[3 * kRow] = sn;
+  }
 }
 
 // ------------------------------------------------------------------------------------

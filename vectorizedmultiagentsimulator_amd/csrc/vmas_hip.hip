@@ -215,7 +215,7 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
     // (cos(inf) = NaN): such environments must not use the distance skip
     if (W.trig_in_args && ((W.trig_mask >> e) & 1ull) && !(ABLATE(args) & 8)) {
       const int tr_row = W.row_tr + 4 * __builtin_popcountll(W.trig_mask & ((1ull << e) - 1ull));
-      write_trig(tile + tr_row * ROWF, v[4], ((W.box_mask >> e) & 1ull) ? VMAS_SHAPE_BOX : VMAS_SHAPE_LINE);
+      write_trig(tile + tr_row * ROWF, v[4], ((W.box_mask >> e) & 1ull) ? 4 : 2);
     }
   }
   if (wv < nA) {
@@ -235,7 +235,7 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
   if (!W.trig_in_args) {  // (more than 64 entities: shapes and offsets from the blob, rotations from the tile)
     for (int e = wv; e < nE && !(ABLATE(args) & 8); e += nw) {
       const int shape = sgpr((int)blob[W.b_ent + e * EW + 1]), tr_off = sgpr((int)blob[W.b_ent + e * EW + 3]);
-      if (tr_off >= 0) write_trig(tile + tr_off, tile[(e * 6 + 4) * ROWF], shape);
+      if (tr_off >= 0) write_trig(tile + tr_off, tile[(e * 6 + 4) * ROWF], shape == VMAS_SHAPE_BOX ? 4 : 2);
     }
     __syncthreads();
   }
@@ -391,8 +391,7 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
           if (fl & VMAS_F_MOVABLE) {  // _apply_action_force core.py:2018-2028
             v2 f = V(Af[0], Af[ROWF]);
             if ((fl & (VMAS_F_MAX_F | VMAS_F_F_RANGE)) && args.lz_g == nullptr) {  // (a pass made again reads the clamped rows)
-              if (fl & VMAS_F_MAX_F) f = clamp_with_norm(f, D.max_f);
-              if (fl & VMAS_F_F_RANGE) f = V(clamp_t(f.x, D.f_range), clamp_t(f.y, D.f_range));
+              f = clamp_action_force(f, fl & VMAS_F_MAX_F, D.max_f, fl & VMAS_F_F_RANGE, D.f_range).f;
               Af[0] = f.x; Af[ROWF] = f.y;
               if (last_sub && live) {  // the clamped force is written back (core.py:2021-2027)
                 float* gf = aft + (long)D.agent_index * 3 * ld + env;
@@ -404,12 +403,7 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
           if (fl & VMAS_F_ROTATABLE) {  // _apply_action_torque core.py:2030-2041
             float t = Af[2 * ROWF];
             if ((fl & (VMAS_F_MAX_T | VMAS_F_T_RANGE)) && args.lz_g == nullptr) {
-              if (fl & VMAS_F_MAX_T) {
-                const float n = fabsf(t);
-                const float nt = (t / n) * D.max_t;
-                t = n > D.max_t ? nt : t;
-              }
-              if (fl & VMAS_F_T_RANGE) t = clamp_t(t, D.t_range);
+              t = clamp_action_torque(t, fl & VMAS_F_MAX_T, D.max_t, fl & VMAS_F_T_RANGE, D.t_range).t;
               Af[2 * ROWF] = t;
               if (last_sub && live) aft[((long)D.agent_index * 3 + 2) * ld + env] = t;
             }
@@ -580,16 +574,9 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
       if (skipped_a && (fl & VMAS_F_MOVABLE)) F = F + V(0.f, 0.f);
       float* dst = state + (long)e * 6 * ld + env;
       if (fl & VMAS_F_MOVABLE) {
-        v2 vel = V(es[2], es[3]);
-        if (substep == 0) vel = V(vel.x * D.one_minus_drag, vel.y * D.one_minus_drag);
-        const rcp_t rm = rcp_of(D.mass);
-        const v2 acc = V(F.x / rm, F.y / rm);
-        vel = V(vel.x + acc.x * sub_dt, vel.y + acc.y * sub_dt);
-        if (fl & VMAS_F_MAX_SPEED) vel = clamp_with_norm(vel, D.max_speed);
-        if (fl & VMAS_F_V_RANGE) vel = V(clamp_t(vel.x, D.v_range), clamp_t(vel.y, D.v_range));
-        v2 np = V(es[0] + vel.x * sub_dt, es[1] + vel.y * sub_dt);
-        if (W.xs == W.xs) np.x = clamp_t(np.x, W.xs);
-        if (W.ys == W.ys) np.y = clamp_t(np.y, W.ys);
+        const v2 vel = integrate_velocity(V(es[2], es[3]), F, D.mass, D.one_minus_drag, substep == 0, sub_dt, fl & VMAS_F_MAX_SPEED,
+                                          D.max_speed, fl & VMAS_F_V_RANGE, D.v_range);
+        const v2 np = integrate_position(V(es[0], es[1]), vel, sub_dt, W.xs, W.ys).p;
         if (last) {
           if (live) { dst[0] = np.x; dst[ld] = np.y; dst[2 * ld] = vel.x; dst[3 * ld] = vel.y; }
           if constexpr (ENV != ENV_NONE) { Es[0] = np.x; Es[ROWF] = np.y; Es[2 * ROWF] = vel.x; Es[3 * ROWF] = vel.y; }
@@ -598,16 +585,14 @@ __global__ __launch_bounds__(TILE*(LEVEL >= 2 ? 8 : MAX_WAVES)) void step_kernel
         }
       }
       if (fl & VMAS_F_ROTATABLE) {
-        float av = es[5];
-        if (substep == 0) av = av * D.one_minus_drag;
-        av = av + (Tq / D.inertia) * sub_dt;
-        const float rot = es[4] + av * sub_dt;
+        const rotation_t rt = integrate_rotation(es[4], es[5], Tq, D.inertia, D.one_minus_drag, substep == 0, sub_dt);
+        const float rot = rt.rot, av = rt.av;
         if (last) {
           if (live) { dst[4 * ld] = rot; dst[5 * ld] = av; }
           if constexpr (ENV != ENV_NONE) { Es[4 * ROWF] = rot; Es[5 * ROWF] = av; }
         } else {
           Es[4 * ROWF] = rot; Es[5 * ROWF] = av;
-          if (D.tr_off >= 0) write_trig(tile + D.tr_off, rot, D.shape);
+          if (D.tr_off >= 0) write_trig(tile + D.tr_off, rot, D.shape == VMAS_SHAPE_BOX ? 4 : 2);
         }
       }
     }

@@ -76,21 +76,7 @@ static_assert(sizeof(DevOwned) == 96, "DevOwned is read as six uint4");
 
 
 
-// cos/sin of the rotation(s) the narrow phase needs (physics.py:300-302, 413)
-__device__ __forceinline__ void write_trig(float* tr, float rot, int shape) {
-  float sn, cs;
-  sincosf(rot, &sn, &cs);  // one range reduction for both (ocml), same values as cosf/sinf
-  tr[0 * ROWF] = cs;
-  tr[1 * ROWF] = sn;
-  if (shape == VMAS_SHAPE_BOX) {
-    const float rot2 = rot + kHalfPi;
-    sincosf(rot2, &sn, &cs);
-    tr[2 * ROWF] = cs;
-    tr[3 * ROWF] = sn;
-  }
-}
-
-// (obb_dist2, seg_obb_gap: vmas_device.h - the balance epilogue uses the separating-axis gap too)
+// (write_trig, obb_dist2, seg_obb_gap: vmas_device.h - the backward kernel and the balance epilogue use them too)
 
 // Register views of descriptors read from the LDS blob (uniform address => broadcast read):
 // control words go to SGPRs, offsets and float parameters stay in (uniform) VGPRs.

@@ -15,6 +15,7 @@ constexpr int TILE = 64;       // environments per block = lanes per wave
 constexpr int MAX_WAVES = 16;  // waves (workers) per tile (8 for the register-heavy box-box level)
 constexpr float kSkipSlack = 1e-3f;  // fp slack of the conservative broad-phase distances
 constexpr int ROWF = TILE;     // floats per LDS row
+static_assert(ROWF == kRow, "write_trig (vmas_device.h) strides by kRow");
 
 struct DevEntity {
   uint32_t flags;

@@ -4,7 +4,8 @@
 //
 // Lane = environment, a block owns a tile of 64 environments, as the forward does.  The launch
 //   1. re-runs the step's substeps from the saved pre-step state with the forward's own device functions (contact_force,
-//      clamp_with_norm, clamp_t, rcp_of: vmas_device.h), so every clamp and contact decision has the forward's bits, and
+//      clamp_action_force / _torque, accelerate, clamp_velocity, integrate_position / _rotation: vmas_device.h), so every
+//      clamp and contact decision has the forward's bits, and
 //      checkpoints per movable entity and substep what the reverse sweep needs: the substep's input position and the
 //      velocity in front of its clamps (4 rows of 64 floats = 1 KB);
 //   2. sweeps the substeps backwards: the integrator's adjoint per entity (entities round-robin over the waves), then the
@@ -53,7 +54,7 @@ int host_fail(const char* msg);  // vmas_hip.hip: sets vmas_last_error(), return
 namespace vjp {
 namespace {
 
-constexpr int ROWF = 64;                 // floats per LDS row = environments per tile
+constexpr int ROWF = kRow;               // floats per LDS row = environments per tile
 constexpr int EW = 20, PW = 14;          // table words per entity / per pair
 constexpr int SS_ROWS = 2, SHAPE_ROWS = 5;  // LDS rows of a sphere-sphere pair / of a line-sphere or box-sphere pair
 // an owner's reference to a pair: index | the pair's first row in its chunk << 16 | shaped << 30 | side << 31
@@ -164,35 +165,6 @@ VD LineAdj closest_point_line_vjp(v2 pos, float c, float s, float half, v2 p, v2
   return r;
 }
 
-// closest_point_box (vmas_device.h) with the index of the winning edge: the same edges are solved and compared in the same
-// order with the same strict <, so the point has the forward's bits
-VD v2 closest_point_box_edge(const seg_t e[4], v2 p, int& edge) {
-  const float c = e[2].c, s = e[2].s, hl = e[2].half, hw = e[0].half;
-  const float dx = p.x - (e[0].pos.x + e[1].pos.x) * 0.5f, dy = p.y - (e[0].pos.y + e[1].pos.y) * 0.5f;
-  const float px = dx * c + dy * s, py = dy * c - dx * s;
-  const float ax = fabsf(px) - hl, ay = fabsf(py) - hw;
-  const float ox = fmaxf(ax, 0.f), oy = fmaxf(ay, 0.f);
-  const float inside = (ax <= 0.f && ay <= 0.f) ? fminf(0.f - ax, 0.f - ay) : 0.f;
-  const float ub = sqrt_n(ox * ox + oy * oy) + inside;
-  const float thr = ub + 1e-4f * ub + 1e-5f * (1.f + hl + hw + fabsf(px) + fabsf(py));
-  const float lb[4] = {fabsf(px - hl), fabsf(px + hl), fabsf(py - hw), fabsf(py + hw)};
-  v2 best = V(kInf, kInf);
-  float dist = kInf;
-  edge = 0;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    if (__any(!(lb[i] > thr))) {
-      const v2 q = closest_point_line<true>(e[i].pos, e[i].c, e[i].s, e[i].half, p);
-      const float d = vnorm(p - q);
-      const bool cl = d < dist;
-      best = cl ? q : best;
-      dist = cl ? d : dist;
-      edge = cl ? i : edge;
-    }
-  }
-  return best;
-}
-
 // What a line-sphere / box-sphere pair gives back: the cotangents of the line's or box's position, of the sphere's
 // position and of the line's or box's rotation.
 struct ShapeAdj { v2 pab, pbb; float rotb; };
@@ -237,7 +209,7 @@ VD ShapeAdj box_sphere_vjp(v2 pa, float c, float s, float c2, float s2, float le
   seg_t be[4];
   box_edges(pa, c, s, c2, s2, length, width, be);
   int edge;
-  const v2 cp = closest_point_box_edge(be, pb, edge);
+  const v2 cp = closest_point_box(be, pb, edge);
   v2 ip = cp;
   float depth = 0.f;
   if (!hollow) ip = inner_point_box(pb, cp, pa, depth);
@@ -279,43 +251,6 @@ VD ShapeAdj box_sphere_vjp(v2 pa, float c, float s, float c2, float s2, float le
   const v2 ob = V(reach * A.posb.x, reach * A.posb.y);  // centre = pa + reach (oc, os)
   R.rotb = (A.ub.y * ec - A.ub.x * es) + (ob.y * oc - ob.x * os);
   return R;
-}
-
-// cos/sin of the rotation(s) the narrow phase needs, as the forward writes them (write_trig, vmas_step_device.h)
-VD void write_trig(float* tr, float rot, int nt) {
-  float sn, cs;
-  sincosf(rot, &sn, &cs);
-  tr[0 * ROWF] = cs;
-  tr[1 * ROWF] = sn;
-  if (nt == 4) {
-    const float rot2 = rot + kHalfPi;
-    sincosf(rot2, &sn, &cs);
-    tr[2 * ROWF] = cs;
-    tr[3 * ROWF] = sn;
-  }
-}
-
-// _apply_action_force's clamps (core.py:2018-2028), as step_kernel applies them
-VD v2 clamp_force(const Ent& D, v2 f) {
-  if (D.flags & VMAS_F_MAX_F) f = clamp_with_norm(f, D.max_f);
-  if (D.flags & VMAS_F_F_RANGE) f = V(clamp_t(f.x, D.f_range), clamp_t(f.y, D.f_range));
-  return f;
-}
-// _apply_action_torque's (core.py:2030-2041); `over`: the norm clamp acted
-VD float clamp_torque(const Ent& D, float t, bool& over) {
-  over = false;
-  if (D.flags & VMAS_F_MAX_T) {
-    const float n = fabsf(t);
-    const float nt = (t / n) * D.max_t;
-    over = n > D.max_t;
-    t = over ? nt : t;
-  }
-  return t;
-}
-// the velocity clamps of _integrate_state (core.py:2872-2879): v1 behind max_speed, the return value behind v_range
-VD v2 clamp_vel(const Ent& D, v2 vpre, v2& v1) {
-  v1 = (D.flags & VMAS_F_MAX_SPEED) ? clamp_with_norm(vpre, D.max_speed) : vpre;
-  return (D.flags & VMAS_F_V_RANGE) ? V(clamp_t(v1.x, D.v_range), clamp_t(v1.y, D.v_range)) : v1;
 }
 
 // SH: the world has line-sphere / box-sphere pairs.  Without them none of their code is in the kernel.
@@ -370,12 +305,9 @@ step_vjp_kernel(const Args A, const float* __restrict__ state_in, const float* _
       write_trig(Q + 4 * ROWF, rot, D.nt);
       Q[1 * ROWF] = X[5 * ld];
       float Tq = 0.f;
-      if ((D.flags & VMAS_F_AGENT) && (D.flags & VMAS_F_ROTATABLE)) {  // _apply_action_torque
-        bool over;
-        float t = clamp_torque(D, ft_in[((long)D.agent_index * 3 + 2) * ld + env], over);
-        if (D.flags & VMAS_F_T_RANGE) t = clamp_t(t, D.t_range);
-        Tq = Tq + t;
-      }
+      if ((D.flags & VMAS_F_AGENT) && (D.flags & VMAS_F_ROTATABLE))  // _apply_action_torque
+        Tq = Tq + clamp_action_torque(ft_in[((long)D.agent_index * 3 + 2) * ld + env], D.flags & VMAS_F_MAX_T, D.max_t,
+                                      D.flags & VMAS_F_T_RANGE, D.t_range).t;
       Q[3 * ROWF] = Tq;
     }
     if (D.flags & VMAS_F_MOVABLE) {
@@ -384,7 +316,7 @@ step_vjp_kernel(const Args A, const float* __restrict__ state_in, const float* _
       v2 F = V(0.f, 0.f);
       if (D.flags & VMAS_F_AGENT) {  // _apply_action_force
         const float* Af = ft_in + (long)D.agent_index * 3 * ld + env;
-        F = F + clamp_force(D, V(Af[0], Af[ld]));
+        F = F + clamp_action_force(V(Af[0], Af[ld]), D.flags & VMAS_F_MAX_F, D.max_f, D.flags & VMAS_F_F_RANGE, D.f_range).f;
       }
       if (A.C.has_gravity) F = F + V(D.mass * A.C.gx, D.mass * A.C.gy);  // _apply_gravity core.py:2043-2052
       if (D.flags & VMAS_F_GRAVITY) F = F + V(D.mass * D.gx, D.mass * D.gy);
@@ -446,33 +378,22 @@ step_vjp_kernel(const Args A, const float* __restrict__ state_in, const float* _
           if (turns) Qr[2 * ROWF] = Tq;
           continue;
         }
-        if (turns) {  // ang_vel' = ang_vel (1 - drag on substep 0) + Tq / I dt, rot' = rot + ang_vel' dt, as step_kernel does it
-          float av = Qr[1 * ROWF];
-          if (s == 0) av = av * D.one_minus_drag;
-          av = av + (Tq / D.inertia) * dt;
-          Qr[1 * ROWF] = av;
+        if (turns) {
+          const rotation_t rt = integrate_rotation(Qr[(4 + D.nt + s) * ROWF], Qr[1 * ROWF], Tq, D.inertia, D.one_minus_drag, s == 0, dt);
+          Qr[1 * ROWF] = rt.av;
           if (s + 1 < S) {
-            const float rot = Qr[(4 + D.nt + s) * ROWF] + av * dt;
-            Qr[(4 + D.nt + s + 1) * ROWF] = rot;
-            write_trig(Qr + 4 * ROWF, rot, D.nt);
+            Qr[(4 + D.nt + s + 1) * ROWF] = rt.rot;
+            write_trig(Qr + 4 * ROWF, rt.rot, D.nt);
           }
         }
         if (!mov) continue;
-        // _integrate_state core.py:2862-2908, as step_kernel does it
         float* K = L + (D.prow + 4 * s) * ROWF;
-        v2 vel = V(R[2 * ROWF], R[3 * ROWF]);
-        if (s == 0) vel = V(vel.x * D.one_minus_drag, vel.y * D.one_minus_drag);
-        const rcp_t rm = rcp_of(D.mass);
-        const v2 acc = V(F.x / rm, F.y / rm);
-        vel = V(vel.x + acc.x * dt, vel.y + acc.y * dt);
-        K[2 * ROWF] = vel.x; K[3 * ROWF] = vel.y;
-        v2 v1;
-        vel = clamp_vel(D, vel, v1);
+        const v2 pre = accelerate(V(R[2 * ROWF], R[3 * ROWF]), F, D.mass, D.one_minus_drag, s == 0, dt);
+        K[2 * ROWF] = pre.x; K[3 * ROWF] = pre.y;
+        const v2 vel = clamp_velocity(pre, D.flags & VMAS_F_MAX_SPEED, D.max_speed, D.flags & VMAS_F_V_RANGE, D.v_range).v;
         R[2 * ROWF] = vel.x; R[3 * ROWF] = vel.y;
         if (s + 1 < S) {  // (the position behind the last substep is not an input of anything)
-          v2 np = V(K[0] + vel.x * dt, K[ROWF] + vel.y * dt);
-          if (clamp_x) np.x = clamp_t(np.x, A.C.xs);
-          if (clamp_y) np.y = clamp_t(np.y, A.C.ys);
+          const v2 np = integrate_position(V(K[0], K[ROWF]), vel, dt, A.C.xs, A.C.ys).p;
           K[4 * ROWF] = np.x; K[5 * ROWF] = np.y;
         }
       }
@@ -513,14 +434,16 @@ step_vjp_kernel(const Args A, const float* __restrict__ state_in, const float* _
       float* R = L + D.arow * ROWF;
       const float* K = L + (D.prow + 4 * s) * ROWF;
       v2 pb = V(R[0], R[ROWF]), vb = V(R[2 * ROWF], R[3 * ROWF]);
-      const v2 vpre = V(K[2 * ROWF], K[3 * ROWF]);
-      v2 v1;
-      const v2 vel = clamp_vel(D, vpre, v1);
-      if (clamp_x) pb.x = pass_clamp(K[0] + vel.x * dt, A.C.xs, pb.x);  // position clamps
-      if (clamp_y) pb.y = pass_clamp(K[ROWF] + vel.y * dt, A.C.ys, pb.y);
-      vb = V(vb.x + pb.x * dt, vb.y + pb.y * dt);                        // pos' = pos + vel' dt
-      if (D.flags & VMAS_F_V_RANGE) vb = V(pass_clamp(v1.x, D.v_range, vb.x), pass_clamp(v1.y, D.v_range, vb.y));
-      if (D.flags & VMAS_F_MAX_SPEED) vb = clamp_with_norm_vjp(vpre, D.max_speed, vb);
+      const v2 pre = V(K[2 * ROWF], K[3 * ROWF]);
+      const velocity_t v = clamp_velocity(pre, D.flags & VMAS_F_MAX_SPEED, D.max_speed, D.flags & VMAS_F_V_RANGE, D.v_range);
+      if (clamp_x || clamp_y) {  // position clamps
+        const v2 np = integrate_position(V(K[0], K[ROWF]), v.v, dt, A.C.xs, A.C.ys).raw;
+        if (clamp_x) pb.x = pass_clamp(np.x, A.C.xs, pb.x);
+        if (clamp_y) pb.y = pass_clamp(np.y, A.C.ys, pb.y);
+      }
+      vb = V(vb.x + pb.x * dt, vb.y + pb.y * dt);  // pos' = pos + vel' dt
+      if (D.flags & VMAS_F_V_RANGE) vb = V(pass_clamp(v.v1.x, D.v_range, vb.x), pass_clamp(v.v1.y, D.v_range, vb.y));
+      if (D.flags & VMAS_F_MAX_SPEED) vb = clamp_with_norm_vjp(pre, D.max_speed, vb);
       const rcp_t rm = rcp_of(D.mass);
       const v2 Fb = V((vb.x * dt) / rm, (vb.y * dt) / rm);              // vel' = vel (1 - drag) + F / m dt
       if (s == 0) vb = V(vb.x * D.one_minus_drag, vb.y * D.one_minus_drag);
@@ -610,17 +533,17 @@ step_vjp_kernel(const Args A, const float* __restrict__ state_in, const float* _
       fb = fb + V(R[6 * ROWF], R[7 * ROWF]);
       const v2 raw = V(ft_in[ao + env], ft_in[ao + ld + env]);
       if (D.flags & VMAS_F_F_RANGE) {
-        const v2 f1 = (D.flags & VMAS_F_MAX_F) ? clamp_with_norm(raw, D.max_f) : raw;
+        const v2 f1 = clamp_action_force(raw, D.flags & VMAS_F_MAX_F, D.max_f, D.flags & VMAS_F_F_RANGE, D.f_range).f1;
         fb = V(pass_clamp(f1.x, D.f_range, fb.x), pass_clamp(f1.y, D.f_range, fb.y));
       }
       if (D.flags & VMAS_F_MAX_F) fb = clamp_with_norm_vjp(raw, D.max_f, fb);
     }
     if (rotb) {
       tb = tb + Tb;
-      bool over;
-      const float t1 = clamp_torque(D, ft_in[ao + 2 * ld + env], over);
-      if (D.flags & VMAS_F_T_RANGE) tb = pass_clamp(t1, D.t_range, tb);
-      tb = over ? 0.f : tb;  // t / |t| max_t does not depend on |t|
+      const action_torque_t t = clamp_action_torque(ft_in[ao + 2 * ld + env], D.flags & VMAS_F_MAX_T, D.max_t, D.flags & VMAS_F_T_RANGE,
+                                                    D.t_range);
+      if (D.flags & VMAS_F_T_RANGE) tb = pass_clamp(t.t1, D.t_range, tb);
+      tb = t.over ? 0.f : tb;  // t / |t| max_t does not depend on |t|
     }
     if (live) { g_ft_in[ao + env0] = fb.x; g_ft_in[ao + ld + env0] = fb.y; g_ft_in[ao + 2 * ld + env0] = tb; }
   }
